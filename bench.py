@@ -7,8 +7,14 @@ substitutions + 2 % indels (seed 101) -- filled into the sparse tile-header (mls
 (tileHrowMat / tileHcolMat, tileBx 256), blosum62, gapo -11.  The path replaced is
 NwAlign_Gpu9_Mlsp_DiagDiagDiag (nwalign_gpu9_mlsp_diagdiagdiag.cu:368-722) timed as align.calc
 (benchmark.cpp:473).  Inputs (sequences, substitution table) are resident in HBM before the
-timed region; the header buffers are preallocated.  The fill's align_cost is checked against
-the oracle golden tests/golden/config3_100k.json (data; no oracle code runs here).
+timed region; the header buffers are preallocated.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does the headline alone: set-up, W untimed and N
+timed fills, one JSON line (value, ms_per_step, the roofline fields computed from the same
+steps).  `--dump-outputs DIR` also writes what the last timed fill left in the header buffers
+(DIR/hrow.npy, DIR/hcol.npy; see dump_outputs).  Everything below is behind `--full`: the
+fill's align_cost checked against the oracle golden tests/golden/config3_100k.json (data; no
+oracle code runs here), the other BASELINE configs as fields of the same line, and the CPU legs.
 
 N>1: one process per GPU (torch.distributed, RCCL); every rank fills its own config-3 pair
 (weak scaling, no data-path collective: RCCL only broadcasts the substitution table and
@@ -609,11 +615,61 @@ def ranks_probe():
     return 0
 
 
+def headline_costs(gsa, geom, hrow, hcol, Y, X, sub, dev, world):
+    """--full: every rank's align_cost of the headline fill and the oracle golden's."""
+    import torch
+    import torch.distributed as dist
+    # align_cost as the reference's mlsp align computes it (recompute of the last tile from its
+    # headers, nwalign_gpu9_mlsp_diagdiagdiag.cu:713-716): only the last tile's headers come back
+    last = geom.tileHdrMatRows * geom.tileHdrMatCols - 1
+    hr = np.zeros(geom.hrowElems, dtype=np.int32)
+    hc = np.zeros(geom.hcolElems, dtype=np.int32)
+    hr[last * geom.tileHrowLen:] = hrow[last * geom.tileHrowLen:].cpu().numpy()
+    hc[last * geom.tileHcolLen:] = hcol[last * geom.tileHcolLen:].cpu().numpy()
+    cost = gsa.sparse_align_cost(gsa.SparseResult(hr, hc, geom, 0, {}), Y, X, sub, -11)
+    del hr, hc
+    costs = [cost]
+    if world > 1:
+        t = torch.tensor([cost], dtype=torch.int64, device=coll_dev(dev))
+        lst = [torch.zeros_like(t) for _ in range(world)]
+        dist.all_gather(lst, t)
+        costs = [int(v.item()) for v in lst]
+    gold = load_golden("config3_100k.json")
+    return costs, None if gold is None else gold["pairs"]["related"]["align_cost"]
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of float64 over all dumped arrays (the files stay under 64 MB in all)
+DUMP_SEED = 7301
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the last timed step left in the caller's buffers, as DIR/<name>.npy
+    in float64 (int32 scores are exact in it).  An array over its share of the budget is written as
+    a fixed sample: the elements at sorted indices drawn from numpy's default_rng(DUMP_SEED + k),
+    the same for every run of the same arguments, gathered on the device."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    per = DUMP_BUDGET_BYTES // 8 // len(arrays)
+    for k, (name, t) in enumerate(arrays):
+        t = t.reshape(-1)
+        if t.numel() > per:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + k).integers(0, t.numel(), size=per, dtype=np.int64))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps of the headline fill")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every secondary field (the golden check of the headline, "
+                         "configs[1], the 100k full matrix, configs[3] and its rank shares, the full-matrix batch, "
+                         "configs[4], the CPU baselines); the --no-* / --*-pairs options below choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's outputs of the last timed step (tileHrowMat, tileHcolMat; a fixed "
+                         "seeded sample of each) as DIR/hrow.npy and DIR/hcol.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--config4-pairs", type=int, default=512, help="0 = skip the configs[3] batch field")
@@ -661,31 +717,18 @@ def main():
     R, C = len(Y) - 1, len(X) - 1
     tY, tX = torch.from_numpy(Y).to(dev), torch.from_numpy(X).to(dev)
     geom = gsa.sparse_geometry(R + 1, C + 1, TILE_BX)
-    hrow = torch.empty(geom.hrowElems, dtype=torch.int32, device=dev)
-    hcol = torch.empty(geom.hcolElems, dtype=torch.int32, device=dev)
+    hrow = torch.zeros(geom.hrowElems, dtype=torch.int32, device=dev)
+    hcol = torch.zeros(geom.hcolElems, dtype=torch.int32, device=dev)
 
     def step():
         eng.fill_sparse_dev(tY.data_ptr(), R + 1, tX.data_ptr(), C + 1, tS.data_ptr(), 25, -11, TILE_BX,
                             hrow.data_ptr(), hcol.data_ptr(), sh)
 
     elapsed, kern_ms = timed_steps(step, stream, dev, a.steps, a.warmup, world, eng)
-    # align_cost as the reference's mlsp align computes it (recompute of the last tile from its
-    # headers, nwalign_gpu9_mlsp_diagdiagdiag.cu:713-716): only the last tile's headers come back
-    last = geom.tileHdrMatRows * geom.tileHdrMatCols - 1
-    hr = np.zeros(geom.hrowElems, dtype=np.int32)
-    hc = np.zeros(geom.hcolElems, dtype=np.int32)
-    hr[last * geom.tileHrowLen:] = hrow[last * geom.tileHrowLen:].cpu().numpy()
-    hc[last * geom.tileHcolLen:] = hcol[last * geom.tileHcolLen:].cpu().numpy()
-    cost = gsa.sparse_align_cost(gsa.SparseResult(hr, hc, geom, 0, {}), Y, X, sub, -11)
-    del hr, hc
-    costs = [cost]
-    if world > 1:
-        t = torch.tensor([cost], dtype=torch.int64, device=coll_dev(dev))
-        lst = [torch.zeros_like(t) for _ in range(world)]
-        dist.all_gather(lst, t)
-        costs = [int(v.item()) for v in lst]
-    gold = load_golden("config3_100k.json")
-    gold_cost = None if gold is None else gold["pairs"]["related"]["align_cost"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [("hrow", hrow), ("hcol", hcol)])
+    if a.full:
+        costs, gold_cost = headline_costs(gsa, geom, hrow, hcol, Y, X, sub, dev, world)
 
     cells = float(R) * float(C)
     value = world * cells * a.steps / elapsed / 1e9
@@ -697,7 +740,7 @@ def main():
 
     # ---- configs[1]: 10k x 10k full matrix (secondary field) ------------------------------
     full10k = None
-    if not a.no_10k:
+    if a.full and not a.no_10k:
         Y2, X2 = config2_pair()
         R2, C2 = len(Y2) - 1, len(X2) - 1
         tY2, tX2 = torch.from_numpy(Y2).to(dev), torch.from_numpy(X2).to(dev)
@@ -724,10 +767,10 @@ def main():
         torch.cuda.empty_cache()
     # ---- the headline pair as a full matrix (40 GB) ----------------------------------------
     full100k = None
-    if not a.no_100k_full:
+    if a.full and not a.no_100k_full:
         full100k = bench_full100k(dev, eng, tS, sh, stream, max(3, a.steps // 4), 2, world)
     cfg5 = None
-    if not a.no_config5:
+    if a.full and not a.no_config5:
         cfg5 = bench_config5(dev, eng, max(3, a.steps // 4), 2, 0 if a.no_cpu_baseline else a.config5_cpu_sample,
                              rank, world)
     eng.sync(sh)
@@ -735,13 +778,13 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- full-matrix family at throughput (HBM-write bound) ------------------------------
-    fullb = bench_full_batch(world, rank, local, a.full_batch_pairs) if a.full_batch_pairs > 0 else None
+    fullb = bench_full_batch(world, rank, local, a.full_batch_pairs) if a.full and a.full_batch_pairs > 0 else None
     torch.cuda.empty_cache()
 
     # ---- configs[3]: 512 pairs, LPT-sharded (strong scaling field) ------------------------
-    cfg4 = bench_config4(world, rank, local, a.config4_pairs) if a.config4_pairs > 0 else None
+    cfg4 = bench_config4(world, rank, local, a.config4_pairs) if a.full and a.config4_pairs > 0 else None
     share = None
-    if a.config4_pairs > 0 and world == 1 and not REHEARSE and not a.no_rank_share:
+    if a.full and a.config4_pairs > 0 and world == 1 and not REHEARSE and not a.no_rank_share:
         share = bench_config4_rank_share(local, a.config4_pairs, cfg4)
 
     if rank == 0:
@@ -765,11 +808,14 @@ def main():
                          "header_GBps": round(hdr_bytes / (kern_ms * 1e-3) / 1e9, 1),
                          "hbm_frac": round(hdr_bytes / (kern_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 5),
                          "critical_path": critical_path(C, -(-R // 256), 9, kern_ms, 256)},
-            "align_costs": costs[:8], "golden_align_cost": gold_cost,
-            "golden_match": None if gold_cost is None else all(c == gold_cost for c in costs),
-            "fill_10k_full": full10k, "fill_100k_full": full100k, "config4": cfg4, "config4_rank_share": share, "full_batch": fullb, "config5": cfg5,
         }
-        if not a.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
+        if a.full:  # a plain run's line ends here: the headline alone
+            out.update({
+                "align_costs": costs[:8], "golden_align_cost": gold_cost,
+                "golden_match": None if gold_cost is None else all(c == gold_cost for c in costs),
+                "fill_10k_full": full10k, "fill_100k_full": full100k, "config4": cfg4,
+                "config4_rank_share": share, "full_batch": fullb, "config5": cfg5})
+        if a.full and not a.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(Y, X, sub, budget_s=a.cpu_budget)
         print(json.dumps(out), flush=True)
     if world > 1:

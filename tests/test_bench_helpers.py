@@ -101,6 +101,24 @@ def test_full_kernel_label(monkeypatch):
     assert "nw_expand_stream_kernel" in bench.full_kernel_name(False)
 
 
+def test_dump_outputs_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files, a small array whole, a large one as the same sorted seeded
+    sample on every call, the budget shared by the arrays."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 2000)
+    big = torch.arange(100000, dtype=torch.int32) * 3 - 7
+    small = torch.tensor([5, -1101045, 447593], dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("big", big), ("small", small)])
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (1000,) and np.array_equal(a, b)
+    idx = ((a + 7) / 3).astype(np.int64)
+    assert np.all(np.diff(idx) >= 0) and idx.min() >= 0 and idx.max() < 100000 and len(set(idx)) > 900
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and s.tolist() == [5.0, -1101045.0, 447593.0]
+
+
 def test_pass_fields_out_fill():
     """full_batch.passes: pass 2's rate beside the runtime fill kernel's over the same output buffer."""
     tm = {"pass1_ms": 4.0, "pass2_ms": 20.0, "out_fill_ms": 16.0, "out_fill_bytes": 110 * 10**9}

@@ -18,5 +18,5 @@ for l in open('gpurun_out/nl_$1.log'):
 done
 for v in "4 1" "2 0" "2 1"; do
   set -- $v
-  GSA_KROW_K=$1 GSA_KROW_Q8=$2 timeout -k 10 120 python -u bench.py --steps 10 --no-10k --no-config5 --no-cpu-baseline --config4-pairs 0 --full-batch-pairs 0 --no-rank-share 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('headline K=$1 q8=$2', j['ms_per_step'], j['value'], j['golden_match'])"
+  GSA_KROW_K=$1 GSA_KROW_Q8=$2 timeout -k 10 120 python -u bench.py --full --steps 10 --no-10k --no-config5 --no-cpu-baseline --config4-pairs 0 --full-batch-pairs 0 --no-rank-share 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('headline K=$1 q8=$2', j['ms_per_step'], j['value'], j['golden_match'])"
 done

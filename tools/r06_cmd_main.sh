@@ -13,7 +13,8 @@ for l in sys.stdin:
     print('fused', j['ms'], j['cost_ok'], 'strip end first/last', j['strip_end_us']['first'], j['strip_end_us']['last'], j['task_dur_us'], j['tasks_done_per_500us'])"
 timeout -k 10 400 python -u -m pytest -x -q --timeout 200 --timeout-method thread tests/test_gpu_full100k.py tests/test_gpu_parity.py > gpurun_out/r06_t$T.log 2>&1 || { tail -30 gpurun_out/r06_t$T.log; exit 1; }
 tail -2 gpurun_out/r06_t$T.log
-timeout -k 10 300 python -u bench.py --steps 4 --warmup 1 --no-cpu-baseline --config4-pairs 0 --no-config5 > gpurun_out/r06_b$T.json 2> gpurun_out/r06_b$T.err
+D=$(dirname $L)
+timeout -k 10 300 python -u bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --config4-pairs 0 --no-config5 > $D/r06_b$T.json 2> $D/r06_b$T.err
 python3 -c "
 import json
 j = json.loads(open('gpurun_out/r06_b$T.json').read().strip().splitlines()[-1])
