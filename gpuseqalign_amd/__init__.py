@@ -21,7 +21,7 @@ import numpy as np
 __all__ = [
     "NwStat", "NwError", "lib", "Engine", "AlignResult", "SparseResult", "PairDev",
     "NwAlgorithm", "get_nw_algorithm_map", "hash_full", "trace_full", "trace_sparse", "hash_sparse",
-    "sparse_align_cost", "sparse_tile_by",
+    "sparse_align_cost", "sparse_tile_by", "KNOB_NAMES", "LAUNCH_KINDS",
 ]
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
@@ -99,6 +99,20 @@ class FullTiming(ctypes.Structure):
                 ("workgroups", ctypes.c_int64), ("fused", ctypes.c_int32), ("groups", ctypes.c_int32)]
 
 
+class LaunchInfo(ctypes.Structure):
+    """gsa_launch_info (include/gsa.h): the instance the last call on a context ran."""
+    _fields_ = [("kind", ctypes.c_int32), ("ns", ctypes.c_int32), ("k", ctypes.c_int32), ("q8", ctypes.c_int32),
+                ("q8_declined", ctypes.c_int32), ("staged", ctypes.c_int32), ("mlsppt", ctypes.c_int32),
+                ("both_ends", ctypes.c_int32), ("npairs", ctypes.c_int32), ("pair_major", ctypes.c_int32),
+                ("trace_band", ctypes.c_int32),
+                ("tickets", ctypes.c_int64), ("band_tiles", ctypes.c_int64)]
+
+
+# enum gsa_launch_kind (include/gsa.h), by value
+LAUNCH_KINDS = ("none", "full_lane", "full_fused", "full_two_launch", "sparse_krow", "sparse_strip", "score_krow",
+                "score_strip", "score_scan", "trace_sparse")
+
+
 class ScoreResult(ctypes.Structure):
     """gsa_score_result (include/gsa.h)."""
     _fields_ = [("score", ctypes.c_int32), ("i_end", ctypes.c_int64), ("j_end", ctypes.c_int64),
@@ -123,6 +137,7 @@ SIGNATURES = {
     "gsa_set_knob": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p]),
     "gsa_set_full_timing": (ctypes.c_int, [_vp, _i32]),
     "gsa_last_full_timing": (ctypes.c_int, [_vp, ctypes.POINTER(FullTiming)]),
+    "gsa_last_launch": (ctypes.c_int, [_vp, ctypes.POINTER(LaunchInfo)]),
     "gsa_sparse_tile_by": (_i32, []),
     "gsa_sparse_geometry": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(SparseGeom)]),
     "gsa_fill_full_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
@@ -172,6 +187,15 @@ SIGNATURES = {
                                             _vp, _vp, ctypes.c_char_p, _i64, ctypes.POINTER(ctypes.c_int64),
                                             ctypes.POINTER(ctypes.c_uint32), _i32p, _vp]),
 }
+
+# the knobs the library knows (kKnobNames, csrc/gsa_capi.hip), in its order; gsa_set_knob refuses others
+KNOB_NAMES = (
+    "GSA_SPARSE_KERNEL", "GSA_KROW_K", "GSA_KROW_NS", "GSA_KROW_Q8", "GSA_LANE_NS",
+    "GSA_LANE_FEED", "GSA_LANE_PAIR", "GSA_FULL_KERNEL", "GSA_FULL_FUSED", "GSA_FULL_SPLIT",
+    "GSA_FUSED_STAGED",
+    "GSA_EXPAND_RR", "GSA_BATCH_ORDER", "GSA_SCORE_SCAN", "GSA_SCORE_KERNEL", "GSA_SCORE_K",
+    "GSA_SCORE_BIDI", "GSA_SCORE_BIDI_SW", "GSA_BIDI_GRAN", "GSA_BIDI_SKEW", "GSA_BIDI_SW_CONT",
+    "GSA_BIDI_LOG", "GSA_TRACE_BAND", "GSA_TRACE_BAND_BUDGET", "GSA_STAMPS")
 
 
 def lib():
@@ -387,6 +411,17 @@ class Engine:
         return {"pass1_ms": f(t.pass1_ms), "pass2_ms": f(t.pass2_ms), "clock_ghz_median": f(t.clock_ghz_median),
                 "clock_ghz_mean": f(t.clock_ghz_mean), "clock_workgroups": int(t.workgroups), "fused": bool(t.fused),
                 "pipelined_groups": int(t.groups)}
+
+    def last_launch(self) -> dict:
+        """Which instance the last fill, score call or device trace on this context ran
+        (gsa_last_launch; a measurement and test aid): "kind" (one of LAUNCH_KINDS) and the fields of
+        gsa_launch_info.  Waits for that launch (q8_declined is written by it).  Raises NwError
+        (errorInvalidValue) when nothing has been launched yet."""
+        li = LaunchInfo()
+        self._check(lib().gsa_last_launch(self._h, ctypes.byref(li)), "gsa_last_launch")
+        d = {k: int(getattr(li, k)) for k, _ in li._fields_}
+        d["kind"] = LAUNCH_KINDS[li.kind]
+        return d
 
     def set_knob(self, name: str, value: Optional[str]):
         """Set a measurement / test switch (GSA_FULL_KERNEL, GSA_KROW_NS, ...) for this context

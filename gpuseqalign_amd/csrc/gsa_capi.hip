@@ -164,6 +164,11 @@ struct gsa_ctx
     void* lap_user = nullptr;
     // the knobs (kKnobNames): the environment when the context was created, then gsa_set_knob
     std::map<std::string, std::string> knobs;
+    // gsa_last_launch: the instance the last call ran (kind 0: nothing launched yet), the stream it
+    // ran on and the epoch its int8 instance writes to ctl[2] when it declines the table
+    gsa_launch_info ll {};
+    hipStream_t ll_stream = nullptr;
+    unsigned ll_epoch0 = 0, ll_epoch = 0;  // first and last epoch of the call (a split batch has two)
 };
 
 namespace {
@@ -324,6 +329,16 @@ void note_launch(gsa_ctx* c)
         std::max<int64_t>(c->mem.locmem_peak_allocs, f.scratch_per_lane * f.threads_per_wg * f.active_wgs);
     c->mem.regmem_peak_allocs =
         std::max<int64_t>(c->mem.regmem_peak_allocs, f.regs_per_lane * 4 * f.threads_per_wg * f.active_wgs);
+}
+
+// gsa_last_launch's record: a fresh one for the launch just decided (the caller fills the rest)
+gsa_launch_info& new_launch_info(gsa_ctx* c, int kind, hipStream_t st, unsigned epoch)
+{
+    c->ll = gsa_launch_info {};
+    c->ll.kind = kind;
+    c->ll_stream = st;
+    c->ll_epoch0 = c->ll_epoch = epoch;
+    return c->ll;
 }
 
 // Read the sticky error word (after the caller's stream sync) and clear it if set.
@@ -539,6 +554,15 @@ int score_bidi(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX
         (e = gsa::launch_krow_score(a, mode, K, std::max(1, std::min(a.nTicketsTotal, ctx->cu_count)), st)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, a.epoch);
+        li.ns = a.ns;
+        li.k = K;
+        li.q8 = q8;
+        li.both_ends = 1;
+        li.npairs = nP;
+        li.tickets = a.nTicketsTotal;
+    }
     // the rows where the halves meet: a lane tap (tap rows, one int per column from kTapPad), or the
     // half's last-ticket granules (the low word of each 64-bit granule)
     const int* gTop = (const int*)(ctx->gran + (size_t)(tkTop - 1) * stride);
@@ -615,6 +639,7 @@ int score_bidi(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX
                     hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             note_launch(ctx);
+            ctx->ll_epoch = ep2;  // (the record stays the both-ends call's; the word is this launch's)
             (void)hipEventRecord(ctx->ev1, st);
             if ((e = hipMemcpyAsync(rw, ctx->sctl, sizeof(rw), hipMemcpyDeviceToHost, st)) != hipSuccess ||
                 (e = hipStreamSynchronize(st)) != hipSuccess)
@@ -737,6 +762,14 @@ int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* 
     if ((e = krow ? gsa::launch_krow_score(a, mode, scoreK, grid, st) : gsa::launch_strip_fill(a, mode, grid, st)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, krow ? GSA_LAUNCH_SCORE_KROW : GSA_LAUNCH_SCORE_STRIP, st, a.epoch);
+        li.ns = a.ns;
+        li.k = krow ? scoreK : 1;
+        li.q8 = krow ? a.q8 : 0;
+        li.npairs = 1;
+        li.tickets = tickets;
+    }
     (void)hipEventRecord(ctx->ev1, st);
     unsigned long long res[4] = {0, 0, 0, 0};
     if ((e = hipMemcpyAsync(res, ctx->sctl, sizeof(res), hipMemcpyDeviceToHost, st)) != hipSuccess ||
@@ -930,7 +963,23 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
     a.sched = sched.empty() ? nullptr : (const int*)(ctx->desc + npairs);
     e = gsa::launch_headers(a, mode, maxWork, st);
     if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-    if (tickets == 0) return GSA_SUCCESS;
+    // gsa_last_launch: the instance decided above (a two-pass full fill's caller then names the kind)
+    auto record = [&](unsigned epoch) {
+        gsa_launch_info& li = new_launch_info(
+            ctx, lane ? GSA_LAUNCH_FULL_LANE : krow ? GSA_LAUNCH_SPARSE_KROW : GSA_LAUNCH_SPARSE_STRIP, st, epoch);
+        li.ns = a.ns;
+        li.k = krow ? krowK : 1;
+        li.q8 = a.q8;
+        li.mlsppt = done ? 1 : 0;
+        li.npairs = npairs;
+        li.pair_major = (npairs > 1 && sched.empty()) ? 1 : 0;
+        li.tickets = tickets;
+    };
+    if (tickets == 0)
+    {
+        record(0);  // headers only
+        return GSA_SUCCESS;
+    }
 
     // granule stride (Cp+1) and base are per pair: the kernel takes them from the descriptor
     if ((s = ensure_gran(ctx, (size_t)gran, st)) != GSA_SUCCESS) return s;
@@ -1022,6 +1071,7 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
                  : gsa::launch_strip_fill(a, mode, grid, st);
     if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
+    record(a.epoch);
     return GSA_SUCCESS;
 }
 
@@ -1076,7 +1126,8 @@ int enqueue_full_twopass(gsa_ctx* ctx, int npairs, const gsa_pair_dev* pairs, co
     // (never inside a split batch: a group of one pair would take the fused branch, which records
     // neither afterP1 nor timeP1, and group B would then start against an unrecorded event)
     const bool fused = interior && !opt.split && npairs == 1 && fusedMode >= 1;
-    const int ns = env_int(ctx, "GSA_KROW_NS", (npairs > 1 && !fitsChip) ? 8 : 4) == 8 ? 8 : 4;  // as enqueue_batch
+    // (as enqueue_batch; the fused launch has its 4-strip instance only: launch_full_fused)
+    const int ns = fused ? 4 : env_int(ctx, "GSA_KROW_NS", (npairs > 1 && !fitsChip) ? 8 : 4) == 8 ? 8 : 4;
     // pass 2 (fused or its own launch): the streamed expansion, kExpStreamWaves - 1 tile waves per
     // workgroup, tasks of that many 64-row tiles
     const int xWaves = gsa::kExpStreamWaves - 1;
@@ -1249,7 +1300,7 @@ int enqueue_full_twopass(gsa_ctx* ctx, int npairs, const gsa_pair_dev* pairs, co
             // step, so it is ready at about s1 lag + cb + cols.  Row-chunk-major order made the first
             // workgroups wait for whole rows: at 100k they claimed row chunk 0's tiles to the far end
             // of the matrix, ready only ~4 ms later (profiles/r06_fused100k.txt).  lag = columns per
-            // 256-row strip, GSA_FUSED_LAG (default 192: the 100k pair's strip-to-strip spacing).
+            // 256-row strip (192: the 100k pair's strip-to-strip spacing).
             const gsa::ExpandPair& d = ex[0];
             constexpr long long lag = 192;
             const int cm = xWaves * xmt;
@@ -1391,6 +1442,8 @@ int enqueue_full_twopass(gsa_ctx* ctx, int npairs, const gsa_pair_dev* pairs, co
     if (s != GSA_SUCCESS) return s;
     if (fused)
     {
+        ctx->ll.kind = GSA_LAUNCH_FULL_FUSED;
+        ctx->ll.staged = staged ? 1 : 0;
         if (timed && (e = hipEventRecord(ctx->pev[2], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
         ctx->timing_state = timed ? 2 : 0;
         return s;
@@ -1402,6 +1455,7 @@ int enqueue_full_twopass(gsa_ctx* ctx, int npairs, const gsa_pair_dev* pairs, co
     if (tuneRecord && (e = hipEventRecord(xt.ev[0], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
     if ((e = gsa::launch_expand_stream(xa, st, xGrid)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
+    ctx->ll.kind = GSA_LAUNCH_FULL_TWO_LAUNCH;  // (pass 1's record, enqueue_batch: the whole call's)
     if (tuneRecord)
     {
         if ((e = hipEventRecord(xt.ev[1], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
@@ -1510,6 +1564,8 @@ int enqueue_full_split(gsa_ctx* ctx, const SplitPlan& sp, bool hasLds, const int
     int r = enqueue_full_twopass(ctx, (int)sp.pa.size(), sp.pa.data(), hasLds ? sp.la.data() : nullptr, subst, substsz,
                                  gapo, st, oa);
     if (r != GSA_SUCCESS) return r;  // (kNoScratch: nothing enqueued yet; the caller's fallback)
+    const gsa_launch_info groupA = ctx->ll;
+    const unsigned epochA = ctx->ll_epoch0;
     r = enqueue_full_twopass(ctx, (int)sp.pb.size(), sp.pb.data(), hasLds ? sp.lb.data() : nullptr, subst, substsz,
                              gapo, ctx->splitstream, ob);
     if (r == kNoScratch)  // no room for a second scratch: group B on the one-pass lane fill
@@ -1524,6 +1580,14 @@ int enqueue_full_split(gsa_ctx* ctx, const SplitPlan& sp, bool hasLds, const int
     if ((e = hipEventRecord(ctx->split_ev[1], ctx->splitstream)) != hipSuccess ||
         (e = hipStreamWaitEvent(st, ctx->split_ev[1], 0)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    // gsa_last_launch: both groups' pairs and tickets, group A's geometry, the caller's stream (which
+    // waits for group B); the int8 word holds either group's epoch (both see the same table)
+    ctx->ll.npairs += groupA.npairs;
+    ctx->ll.tickets += groupA.tickets;
+    ctx->ll.kind = groupA.kind;
+    ctx->ll.ns = groupA.ns;
+    ctx->ll_stream = st;
+    ctx->ll_epoch0 = epochA;
     if (timed)
     {
         if ((e = hipEventRecord(ctx->pev[2], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
@@ -1728,6 +1792,25 @@ int gsa_last_full_timing(gsa_ctx* ctx, gsa_full_timing* out)
     std::nth_element(ghz.begin(), ghz.begin() + ghz.size() / 2, ghz.end());
     out->clock_ghz_median = ghz[ghz.size() / 2];
     out->clock_ghz_mean = (float)(cyc / ticks * 0.1);
+    return GSA_SUCCESS;
+}
+
+int gsa_last_launch(gsa_ctx* ctx, gsa_launch_info* out)
+{
+    if (!ctx || !out) return GSA_ERROR_INVALID_VALUE;
+    std::memset(out, 0, sizeof(*out));
+    if (ctx->ll.kind == GSA_LAUNCH_NONE) return GSA_ERROR_INVALID_VALUE;  // nothing launched yet
+    *out = ctx->ll;
+    // the int8 instance's decline: its launch's epoch in ctl[2] (nw_krow.hip), read behind the launch
+    if (ctx->ll.q8 != 0 && ctx->ll_epoch != 0)
+    {
+        unsigned word = 0;
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->ll_stream);  // the launch's stream only
+        if (e == hipSuccess) e = hipMemcpy(&word, ctx->ctl + 2, sizeof(word), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        out->q8_declined = (word - ctx->ll_epoch0 <= ctx->ll_epoch - ctx->ll_epoch0) ? 1 : 0;
+    }
     return GSA_SUCCESS;
 }
 
@@ -2487,6 +2570,10 @@ int gsa_trace_sparse_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, con
             if ((e = gsa::launch_trace_band(a, ctx->tlist, n, 4 * ctx->cu_count, st)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
         }
+        gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_TRACE_SPARSE, st, 0);
+        li.npairs = 1;
+        li.trace_band = band;
+        li.band_tiles = have ? n : 0;
     }
     if ((e = gsa::launch_trace_sparse(a, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     long long res[2] = {0, 0};
@@ -2603,6 +2690,11 @@ int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int
     (void)hipEventRecord(ctx->ev0, st);
     if ((e = gsa::launch_score_scan(a, local, ctx->cu_count, st)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_SCAN, st, 0);
+        li.k = 1;
+        li.npairs = 1;
+    }
     (void)hipEventRecord(ctx->ev1, st);
     unsigned long long ctl[3];
     if ((e = hipMemcpyAsync(ctl, ctx->sctl, sizeof(ctl), hipMemcpyDeviceToHost, st)) != hipSuccess ||

@@ -132,7 +132,7 @@ def shard_align(pairs: List[Tuple[np.ndarray, np.ndarray]], subst: Optional[np.n
 
 def gpu_batch_align(device: int = 0, mode: str = "sparse", tileBx: int = 256, repeats: int = 1,
                     out_budget_bytes: Optional[int] = None, warmup: int = 0, pitched: bool = True,
-                    timing: Optional[dict] = None) -> AlignBatchFn:
+                    timing: Optional[dict] = None, launch: Optional[dict] = None) -> AlignBatchFn:
     """The GPU `align_batch` of one rank: inputs uploaded before the timed region, then the
     rank's pairs in as few persistent launches as the output memory allows (one launch for
     the whole share when it fits `out_budget_bytes`, default 60 % of free HBM): the launch's
@@ -143,7 +143,8 @@ def gpu_batch_align(device: int = 0, mode: str = "sparse", tileBx: int = 256, re
     pitch, cell (1, 0) on a 128-byte boundary), as the reference keeps its device matrix padded
     (nwalign_gpu3_ml_diagdiag.cu:315-325); False: unpadded adjrows x adjcols.
     timing (full mode): a dict that receives the last launch's pass times and pass 2's effective
-    clock (Engine.last_full_timing; the events are recorded in every launch, read once at the end)."""
+    clock (Engine.last_full_timing; the events are recorded in every launch, read once at the end).
+    launch: a dict that receives Engine.last_launch() of the last launch (the instance it ran)."""
     import torch
     from . import Engine, sparse_geometry, sparse_align_cost, SparseResult, full_pitch, full_base_offset
 
@@ -256,6 +257,8 @@ def gpu_batch_align(device: int = 0, mode: str = "sparse", tileBx: int = 256, re
         eng.sync(stream.cuda_stream)
         torch.cuda.synchronize(dev)
         secs = (time.perf_counter() - t0) / max(1, repeats)
+        if launch is not None:
+            launch.update(eng.last_launch())
         if timing is not None and mode != "sparse":
             timing.update(eng.last_full_timing())
             # the same bytes written by the runtime's fill kernel (after the results were gathered):

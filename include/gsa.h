@@ -218,6 +218,45 @@ typedef struct gsa_full_timing
 int gsa_set_full_timing(gsa_ctx* ctx, int32_t on);
 int gsa_last_full_timing(gsa_ctx* ctx, gsa_full_timing* out);
 
+/* Measurement and test aid, not part of the reference's interface: which instance the last call on
+ * this context ran, as the host decided it at the launch (after every fallback), so a test or a
+ * probe that sets a knob can see that the knob reached the library.  Fills, score calls and the
+ * device trace each overwrite the whole record; fields that do not apply to a kind are 0. */
+enum gsa_launch_kind
+{
+    GSA_LAUNCH_NONE = 0,
+    GSA_LAUNCH_FULL_LANE = 1,       /* one-pass lane fill (nw_lane.hip) */
+    GSA_LAUNCH_FULL_FUSED = 2,      /* two-pass full fill, both passes in one launch */
+    GSA_LAUNCH_FULL_TWO_LAUNCH = 3, /* two-pass full fill, pass 1 and the expansion as two launches */
+    GSA_LAUNCH_SPARSE_KROW = 4,     /* K-rows sparse fill (nw_krow.hip) */
+    GSA_LAUNCH_SPARSE_STRIP = 5,    /* strip sparse fill (nw_strip.hip) */
+    GSA_LAUNCH_SCORE_KROW = 6,      /* K-rows score kernel */
+    GSA_LAUNCH_SCORE_STRIP = 7,     /* strip kernel's score modes */
+    GSA_LAUNCH_SCORE_SCAN = 8,      /* row scan (nw_scan.hip) */
+    GSA_LAUNCH_TRACE_SPARSE = 9     /* gsa_trace_sparse_dev */
+};
+typedef struct gsa_launch_info
+{
+    int32_t kind;        /* enum gsa_launch_kind */
+    int32_t ns, k;       /* strips per workgroup and rows per lane as passed to the launcher (lane fill:
+                          * ns lane strips, k = 1; a full two-pass fill: pass 1's; strip kernel: 4, 1) */
+    int32_t q8;          /* K-rows kernels: 0 = the int16 profile only, 1 = the int8 instance with the
+                          * int16 one behind it */
+    int32_t q8_declined; /* 1: the int8 instance declined the table and the int16 one ran */
+    int32_t staged;      /* fused full fill: row 64m through the storer wave */
+    int32_t mlsppt;      /* sparse fill launched by gsa_align_sparse_pt */
+    int32_t both_ends;   /* score: the pair ran from both ends */
+    int32_t npairs;
+    int32_t pair_major;  /* a batch's tickets pair by pair (GSA_BATCH_ORDER=pair), not round-robin */
+    int32_t trace_band;  /* device trace: the band used (GSA_TRACE_BAND), columns */
+    int64_t tickets;     /* fills and strip / K-rows scores: tickets of the (pass-1) launch */
+    int64_t band_tiles;  /* device trace: tiles precomputed around the diagonal (0: the walk alone) */
+} gsa_launch_info;
+/* errorInvalidValue: nothing launched yet.  q8_declined is a word the launch writes on the device, so
+ * for a launch with q8 = 1 this synchronizes the stream of that launch (as gsa_debug_stamps does)
+ * before it reads it. */
+int gsa_last_launch(gsa_ctx* ctx, gsa_launch_info* out);
+
 /* ---- consumers (host), the reference's L4 ----------------------------------------- */
 /* NwHash1_Plain (src/nwtrace1_plain.cpp:133-154). */
 uint32_t gsa_hash_full(const int32_t* score, int32_t adjrows, int32_t adjcols);

@@ -1,6 +1,7 @@
 """The C-ABI library: loads, exports every symbol include/gsa.h declares, and its host-side
 consumers (Trace1/Hash1/Trace2/Hash2, src/nwtrace1_plain.cpp / src/nwtrace2_sparse.cpp)
 agree with the oracle.  No GPU compute here."""
+import ctypes
 import os
 import re
 
@@ -26,6 +27,24 @@ def test_library_exports_header():
     for name in decl:
         assert hasattr(L, name), name
         assert name in gsa.SIGNATURES, name
+
+
+def test_last_launch_binding_matches_header():
+    """gsa_launch_info / enum gsa_launch_kind in gsa.h against the ctypes mirror: the same fields in
+    the same order (int32_t / int64_t only), the same kinds by value; no context: errorInvalidValue."""
+    text = open(os.path.join(ROOT, "include", "gsa.h")).read()
+    body = re.search(r"typedef struct gsa_launch_info\s*\{(.*?)\}\s*gsa_launch_info;", text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for ctype, names in re.findall(r"\b(int32_t|int64_t)\s+([^;]+);", body):
+        fields += [(n.strip(), ctypes.c_int32 if ctype == "int32_t" else ctypes.c_int64) for n in names.split(",")]
+    assert fields == list(gsa.LaunchInfo._fields_)
+    enum = re.search(r"enum gsa_launch_kind\s*\{(.*?)\};", text, re.S).group(1)
+    kinds = re.findall(r"GSA_LAUNCH_([A-Z_]+)\s*=\s*(\d+)", enum)
+    assert [int(v) for _, v in kinds] == list(range(len(kinds)))
+    assert tuple(n.lower() for n, _ in kinds) == gsa.LAUNCH_KINDS
+    li = gsa.LaunchInfo()
+    assert gsa.lib().gsa_last_launch(None, ctypes.byref(li)) == gsa.NwStat.errorInvalidValue
 
 
 def test_geometry():

@@ -52,6 +52,8 @@ def test_overlap_other_geometries(engine, golden, monkeypatch, kern, ns, k, knob
     knobs("GSA_KROW_NS", str(ns))
     knobs("GSA_KROW_K", str(k))
     b = engine.align_sparse(Y, X, golden.blosum62, -11, tileBx=128, overlap=True)
+    ll = engine.last_launch()  # the documented fallback, whatever was asked
+    assert (ll["kind"], ll["ns"], ll["k"], ll["mlsppt"]) == ("sparse_krow", 4, 4, 1), ll
     assert np.array_equal(a.hrow, b.hrow) and np.array_equal(a.hcol, b.hcol)
     assert a.align_cost == b.align_cost == oracle.fill_full(Y, X, golden.blosum62, -11)[1]
 

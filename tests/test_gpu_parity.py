@@ -299,8 +299,54 @@ def test_full_fill_kernels(engine, golden, kernel, R, C, monkeypatch, knobs):
         knobs("GSA_FUSED_STAGED", "1")
     Y, X = random_pair(R, C, 13 * R + C)
     r = engine.align_full(Y, X, golden.blosum62, -11)
+    ll = engine.last_launch()
+    want = {"lane": "full_lane", "twopass": "full_two_launch", "fused": "full_fused", "fused_staged": "full_fused"}
+    assert ll["kind"] == want[kernel] and ll["staged"] == (1 if kernel == "fused_staged" else 0), ll
     S, cost = oracle.fill_full(Y, X, golden.blosum62, -11)
     assert np.array_equal(r.score, S) and r.align_cost == cost
+
+
+@pytest.mark.parametrize("pitched", [False, True])
+@pytest.mark.parametrize("R,C", [(2100, 1900), (1, 700)])
+def test_single_pair_full_fill_with_krow_ns_8(engine, golden, knobs, R, C, pitched):
+    """GSA_KROW_NS=8 (a tuning knob of the batch fills) and everything else default: a single pair's
+    full fill is the fused launch, which has its 4-strip instance only, so it runs with ns 4 whatever
+    the knob says (it used to pass 8 on, and the launcher refused it: errorKernelFailure, no fill).
+    Unpadded and gsa_full_pitch layouts, every cell against the oracle, the words around the matrix
+    untouched; a two-pair batch under the same knob still runs its 8-strip pass 1."""
+    import torch
+    knobs("GSA_KROW_NS", "8")
+    dev = torch.device("cuda:0")
+    s = torch.from_numpy(golden.blosum62).to(dev)
+    Y, X = random_pair(R, C, 13 * R + C)
+    S, _ = oracle.fill_full(Y, X, golden.blosum62, -11)
+    y, x = torch.from_numpy(Y).to(dev), torch.from_numpy(X).to(dev)
+    ld = gsa.full_pitch(len(X)) if pitched else len(X)
+    off = gsa.full_base_offset() if pitched else 0
+    n = len(Y) * ld
+    b = torch.full((n + 64 + off,), -7, dtype=torch.int32, device=dev)
+    engine.fill_full_dev(y.data_ptr(), len(Y), x.data_ptr(), len(X), s.data_ptr(), 25, -11, b.data_ptr() + 4 * off,
+                         ld=ld if pitched else None)
+    engine.sync()
+    ll = engine.last_launch()
+    assert (ll["kind"], ll["ns"], ll["k"], ll["npairs"]) == ("full_fused", 4, 4, 1), ll
+    out = b.cpu().numpy()
+    assert np.array_equal(out[off:off + n].reshape(len(Y), ld)[:, :len(X)], S)
+    assert (out[:off] == -7).all() and (out[off + n:] == -7).all()
+    # the batch path is unchanged: two pairs, pass 1 on 8 strips
+    Y2, X2 = random_pair(700, 300, 5)
+    S2, _ = oracle.fill_full(Y2, X2, golden.blosum62, -11)
+    y2, x2 = torch.from_numpy(Y2).to(dev), torch.from_numpy(X2).to(dev)
+    b1 = torch.empty(len(Y) * len(X), dtype=torch.int32, device=dev)
+    b2 = torch.empty(len(Y2) * len(X2), dtype=torch.int32, device=dev)
+    engine.fill_batch_dev([(y.data_ptr(), len(Y), x.data_ptr(), len(X), b1.data_ptr()),
+                           (y2.data_ptr(), len(Y2), x2.data_ptr(), len(X2), b2.data_ptr())], s.data_ptr(), 25, -11,
+                          mode="full")
+    engine.sync()
+    ll = engine.last_launch()
+    assert (ll["kind"], ll["ns"], ll["k"], ll["npairs"]) == ("full_two_launch", 8, 4, 2), ll
+    assert np.array_equal(b1.cpu().numpy().reshape(len(Y), len(X)), S)
+    assert np.array_equal(b2.cpu().numpy().reshape(len(Y2), len(X2)), S2)
 
 
 @pytest.mark.parametrize("ns", ["4", "8"])

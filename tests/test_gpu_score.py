@@ -75,6 +75,7 @@ def test_row_scan_path(engine, golden, R, C, go, ge, local, monkeypatch, knobs):
     knobs("GSA_SCORE_SCAN", "1")
     Y, X = random_pair(R, C, 5 * R + C)
     r = engine.score(Y, X, golden.blosum62, go, ge, local)
+    assert engine.last_launch()["kind"] == "score_scan"
     assert (r["score"], r["i_end"], r["j_end"]) == oracle.score_ag(Y, X, golden.blosum62, go, ge, local)
 
 
@@ -140,6 +141,7 @@ def test_strip_kernel_path(engine, golden, R, C, go, ge, local, monkeypatch, kno
     knobs("GSA_SCORE_KERNEL", "strip")
     Y, X = random_pair(R, C, 7 * R + C)
     r = engine.score(Y, X, golden.blosum62, go, ge, local)
+    assert engine.last_launch()["kind"] == "score_strip"
     assert (r["score"], r["i_end"], r["j_end"]) == oracle.score_ag(Y, X, golden.blosum62, go, ge, local)
 
 
@@ -154,6 +156,8 @@ def test_result_row_positions(engine, golden, monkeypatch, k, R, go, ge, local, 
     knobs("GSA_SCORE_K", k)
     Y, X = random_pair(R, 257, R + 11)
     r = engine.score(Y, X, golden.blosum62, go, ge, local)
+    ll = engine.last_launch()
+    assert ll["kind"] == "score_krow" and ll["k"] == int(k), ll
     assert (r["score"], r["i_end"], r["j_end"]) == oracle.score_ag(Y, X, golden.blosum62, go, ge, local)
 
 

@@ -33,12 +33,15 @@ def _pair(R, C, related, seed):
 
 
 @pytest.mark.parametrize("ns,k", [(4, 4), (8, 4), (2, 2)])
-def test_random_shapes_match_oracle(engine, golden, monkeypatch, ns, k):
-    monkeypatch.setenv("GSA_KROW_NS", str(ns))
-    monkeypatch.setenv("GSA_KROW_K", str(k))
-    for R, C, tBx, related, seed in _shapes(100 * ns + k, 12):
+def test_random_shapes_match_oracle(engine, golden, knobs, ns, k):
+    knobs("GSA_KROW_NS", str(ns))
+    knobs("GSA_KROW_K", str(k))
+    for n, (R, C, tBx, related, seed) in enumerate(_shapes(100 * ns + k, 12)):
         Y, X = _pair(R, C, related, seed)
         res = engine.align_sparse(Y, X, golden.blosum62, -11, tileBx=tBx)
+        if n == 0:  # the geometry asked for is the one that ran
+            ll = engine.last_launch()
+            assert (ll["kind"], ll["ns"], ll["k"]) == ("sparse_krow", ns, k), ll
         hr, hc, _, _, cost = oracle.sparse_headers(Y, X, golden.blosum62, -11, gsa.sparse_tile_by(), tBx)
         assert np.array_equal(res.hrow, hr) and np.array_equal(res.hcol, hc), (len(Y), len(X), tBx, related)
         assert res.align_cost == cost

@@ -10,9 +10,9 @@ from tests._data import random_pair
 
 
 @pytest.mark.gpu
-def test_full_timing_two_launches(engine, golden, monkeypatch):
+def test_full_timing_two_launches(engine, golden, knobs):
     import torch
-    monkeypatch.setenv("GSA_FULL_FUSED", "0")
+    knobs("GSA_FULL_FUSED", "0")
     pairs = [random_pair(r, c, 7 * r + c) for r, c in ((2100, 1900), (700, 3000))]
     dev = torch.device("cuda:0")
     s = torch.from_numpy(golden.blosum62).to(dev)
@@ -28,6 +28,8 @@ def test_full_timing_two_launches(engine, golden, monkeypatch):
     finally:
         engine.set_full_timing(False)
     engine.sync()
+    ll = engine.last_launch()
+    assert ll["kind"] == "full_two_launch" and ll["npairs"] == 2, ll
     assert not t["fused"] and t["pass1_ms"] > 0 and t["pass2_ms"] > 0
     assert t["clock_workgroups"] > 0 and 0.3 < t["clock_ghz_median"] < 3.5 and 0.3 < t["clock_ghz_mean"] < 3.5
     for (Y, X), b in zip(pairs, bufs):
@@ -36,9 +38,9 @@ def test_full_timing_two_launches(engine, golden, monkeypatch):
 
 
 @pytest.mark.gpu
-def test_full_timing_fused(engine, golden, monkeypatch):
+def test_full_timing_fused(engine, golden, knobs):
     import torch
-    monkeypatch.setenv("GSA_FULL_FUSED", "1")
+    knobs("GSA_FULL_FUSED", "1")
     Y, X = random_pair(1500, 1300, 5)
     dev = torch.device("cuda:0")
     s = torch.from_numpy(golden.blosum62).to(dev)
@@ -50,6 +52,8 @@ def test_full_timing_fused(engine, golden, monkeypatch):
         t = engine.last_full_timing()
     finally:
         engine.set_full_timing(False)
+    ll = engine.last_launch()
+    assert ll["kind"] == "full_fused" and ll["npairs"] == 1, ll
     assert t["fused"] and t["pass1_ms"] is None and t["pass2_ms"] > 0 and t["clock_ghz_median"] is None
     S, _ = oracle.fill_full(Y, X, golden.blosum62, -11)
     assert np.array_equal(b.cpu().numpy().reshape(len(Y), len(X)), S)

@@ -130,10 +130,10 @@ def test_gpu_batch_matches_oracle(golden, mode):
 @pytest.mark.gpu
 @pytest.mark.parametrize("order", ["round-robin", "pair"])
 @pytest.mark.parametrize("mode", ["full", "sparse"])
-def test_batched_launch_equals_single_fills(engine, golden, mode, order, monkeypatch):
+def test_batched_launch_equals_single_fills(engine, golden, mode, order, knobs):
     """Every output word of a batched launch equals the single-pair fill of the same pair, with
     the tickets scheduled round-robin over the pairs (default) or pair-major (GSA_BATCH_ORDER)."""
-    monkeypatch.setenv("GSA_BATCH_ORDER", order)
+    knobs("GSA_BATCH_ORDER", order)
     import torch
     import gpuseqalign_amd as gsa
     # + pairs of 2-5 tickets (256-row super-strips), so the schedule interleaves their chains
@@ -154,6 +154,8 @@ def test_batched_launch_equals_single_fills(engine, golden, mode, order, monkeyp
         outs.append(o)
     engine.fill_batch_dev(descs, ts.data_ptr(), 25, -11, mode=mode, tileBx=64)
     engine.sync()
+    ll = engine.last_launch()  # the order asked for is the one the launch took
+    assert ll["npairs"] == len(pairs) and ll["pair_major"] == (1 if order == "pair" else 0), ll
     for (y, x), o in zip(pairs, outs):
         if mode == "sparse":
             r = engine.align_sparse(y, x, golden.blosum62, -11, tileBx=64)
