@@ -181,6 +181,8 @@ SIGNATURES = {
                                           _vp]),
     "gsa_score_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
                                      ctypes.POINTER(ScoreResult), _vp]),
+    "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
+                                           ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score": (ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -475,6 +477,42 @@ class Engine:
         self._check(st, "gsa_score_dev")
         return {"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end),
                 "kernel_ms": float(r.calc_kernel_ms)}
+
+    def score_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                        local: bool = False, stream: Optional[int] = None) -> list:
+        """Score-only alignment of many device-resident pairs in one persistent launch
+        (gsa_score_batch_dev; synchronous).  `pairs`: sequence of (seqY_ptr, adjrows, seqX_ptr,
+        adjcols).  One dict per pair, in order, equal to score_dev's for that pair alone except
+        "kernel_ms", which is the hipEvent time of the whole call's kernels in every dict."""
+        n = len(pairs)
+        arr = (PairDev * max(n, 1))()
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+        res = (ScoreResult * max(n, 1))()
+        ms = ctypes.c_float(0.0)
+        st = lib().gsa_score_batch_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                       int(local), res, ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_batch_dev")
+        return [{"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end), "kernel_ms": float(ms.value)}
+                for r in res[:n]]
+
+    def score_batch(self, pairs, subst, gapo: int, gape: Optional[int] = None, local: bool = False) -> list:
+        """score_batch_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the header
+        element in front, as score() takes them; sequences and table are uploaded through torch.
+        One dict per pair: {"score", "i_end", "j_end", "kernel_ms"}."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS = up(subst.ravel())
+        keep, ptrs = [], []
+        for y, x in pairs:
+            dY, dX = up(y), up(x)
+            keep.append((dY, dX))
+            ptrs.append((dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel()))
+        torch.cuda.synchronize(dev)
+        return self.score_batch_dev(ptrs, dS.data_ptr(), substsz, gapo, gape, local)
 
     # -- device-side verification (SURVEY.md 8(f)1) ---------------------------------------
 

@@ -151,6 +151,10 @@ struct gsa_ctx
     // score-only control words: row scan [0] ticket|err, [1] best key, [2] result; AG/SW strip
     // [0] result, [1] best key, [3] its own error word (the fills' sticky word is not touched)
     unsigned long long* sctl = nullptr;
+    // score batch (gsa_score_batch_dev): two result words per pair, then the decoded answers
+    // (gsa::ScoreOut per pair and one for the error word); grow-only
+    void* sbatch = nullptr;
+    size_t sbatch_cap = 0;  // bytes
     // copy-back of the host-buffer entry points into pageable caller memory: per copy thread a
     // stream and two pinned chunks (DMA of chunk k+1 overlaps the host copy of chunk k)
     static constexpr int kCopyThreads = 8;
@@ -313,7 +317,7 @@ long long held_bytes(const gsa_ctx* c)
                   (long long)c->tband_cap + (long long)c->tlist_cap * 4 + (long long)c->excap +
                   (long long)c->exdesc_cap + (long long)c->excap2 + (long long)c->exdesc_cap2 +
                   8 * (long long)(c->xdone_cap + c->stamps_cap + c->clk_cap) +
-                  4 * (long long)c->bidi_cap;
+                  4 * (long long)c->bidi_cap + (long long)c->sbatch_cap;
     for (size_t k : c->dcap) b += (long long)k;
     return b;
 }
@@ -396,11 +400,7 @@ bool score_kernel_krow(const gsa_ctx* ctx)
 
 // SW end-cell keys: score << bits | (2^bits-1 - row-major index), bits = ceil(log2((R+1)(C+1)));
 // scores (< 2^31) keep 63 - bits >= 29 bits up to (R+1)(C+1) = 2^34
-int sw_idx_bits(int64_t R, int64_t C)
-{
-    const unsigned long long n = (unsigned long long)(R + 1) * (unsigned long long)(C + 1) - 1;
-    return n ? 64 - __builtin_clzll(n) : 1;
-}
+int sw_idx_bits(int64_t R, int64_t C) { return gsa::sw_idx_bits(R, C); }
 
 // Score-only NW from both ends (nw_bidi.h): a single pair's wavefront time is (C + strips x hop)
 // steps, and at 50k the strips' fill-in is ~30 % of it; the top half (rows 1..m) forward and the
@@ -809,6 +809,65 @@ struct FusedLaunch
     bool staged;  // nw_full_fused_kernel's row-64m hand-off through a storer wave (PTF 3), else direct
 };
 
+// Batch schedule (more than one pair): round-robin over the pairs, longest first, so the resident
+// workgroups run the first tickets of every pair side by side instead of one pair's chain of
+// dependent tickets; ticket j of a pair stays behind its ticket j-1.  Two ints per ticket, {pair,
+// ticket within the pair}; empty for one pair or with GSA_BATCH_ORDER=pair (pair-major, comparisons).
+std::vector<int> batch_schedule(const gsa_ctx* ctx, const std::vector<gsa::PairDesc>& hd, long long tickets)
+{
+    std::vector<int> sched;
+    const int npairs = (int)hd.size();
+    const char* order = knob(ctx, "GSA_BATCH_ORDER");
+    if (npairs > 1 && !(order && std::strcmp(order, "pair") == 0))
+    {
+        std::vector<int> ord((size_t)npairs);
+        for (int p = 0; p < npairs; ++p) ord[(size_t)p] = p;
+        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return hd[(size_t)x].nTickets > hd[(size_t)y].nTickets; });
+        sched.reserve(2 * (size_t)tickets);
+        for (int j = 0; j < hd[(size_t)ord[0]].nTickets; ++j)
+            for (int p : ord)
+            {
+                if (hd[(size_t)p].nTickets <= j) break;
+                sched.push_back(p);
+                sched.push_back(j);
+            }
+    }
+    return sched;
+}
+
+// The descriptors, then the schedule, into one device buffer (ctx->desc, units of PairDesc): staged
+// in a pinned slot and copied in stream order.
+int stage_descs(gsa_ctx* ctx, const std::vector<gsa::PairDesc>& hd, const std::vector<int>& sched, hipStream_t st)
+{
+    const size_t npairs = hd.size();
+    const size_t schedUnits = (sched.size() * sizeof(int) + sizeof(gsa::PairDesc) - 1) / sizeof(gsa::PairDesc);
+    const size_t units = npairs + schedUnits;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    int s = ensure_desc(ctx, units);
+    if (s != GSA_SUCCESS) return s;
+    const int slot = ctx->stage_next;
+    ctx->stage_next = (slot + 1) % gsa_ctx::kStage;
+    if (ctx->stage_used[slot] && (e = hipEventSynchronize(ctx->stage_ev[slot])) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    if (ctx->stage_cap[slot] < units)
+    {
+        if (ctx->stage[slot]) (void)hipHostFree(ctx->stage[slot]);
+        ctx->stage[slot] = nullptr;
+        ctx->stage_cap[slot] = 0;
+        if ((e = hipHostMalloc((void**)&ctx->stage[slot], units * sizeof(gsa::PairDesc))) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_ALLOCATION);
+        ctx->stage_cap[slot] = units;
+    }
+    std::memcpy(ctx->stage[slot], hd.data(), npairs * sizeof(gsa::PairDesc));
+    if (!sched.empty()) std::memcpy(ctx->stage[slot] + npairs, sched.data(), sched.size() * sizeof(int));
+    e = hipMemcpyAsync(ctx->desc, ctx->stage[slot], units * sizeof(gsa::PairDesc), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->stage_ev[slot], st);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    ctx->stage_used[slot] = true;
+    return GSA_SUCCESS;
+}
+
 // One batched launch: headers of every pair, then the persistent strip kernel over the
 // tickets of all pairs (pair-major).  `pairs` holds device pointers.
 int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
@@ -910,52 +969,10 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
         gran += (long long)d.nTickets * gsa::gran_stride(d.Cp);
         if (tickets > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
     }
-    // batch schedule (more than one pair): round-robin over the pairs, longest first, so the
-    // resident workgroups run the first tickets of every pair side by side instead of one pair's
-    // chain of dependent tickets; ticket j of a pair stays behind its ticket j-1
-    std::vector<int> sched;
-    const char* order = knob(ctx, "GSA_BATCH_ORDER");  // "pair": pair-major (comparisons)
-    if (npairs > 1 && !(order && std::strcmp(order, "pair") == 0))
-    {
-        std::vector<int> ord((size_t)npairs);
-        for (int p = 0; p < npairs; ++p) ord[(size_t)p] = p;
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return hd[(size_t)x].nTickets > hd[(size_t)y].nTickets; });
-        sched.reserve(2 * (size_t)tickets);
-        for (int j = 0; j < hd[(size_t)ord[0]].nTickets; ++j)
-            for (int p : ord)
-            {
-                if (hd[(size_t)p].nTickets <= j) break;
-                sched.push_back(p);
-                sched.push_back(j);
-            }
-    }
-    // descriptors, then the schedule, in one device buffer (units of PairDesc)
-    const size_t schedUnits = (sched.size() * sizeof(int) + sizeof(gsa::PairDesc) - 1) / sizeof(gsa::PairDesc);
-    const size_t units = (size_t)npairs + schedUnits;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-    int s = ensure_desc(ctx, units);
+    const std::vector<int> sched = batch_schedule(ctx, hd, tickets);
+    hipError_t e;
+    int s = stage_descs(ctx, hd, sched, st);
     if (s != GSA_SUCCESS) return s;
-    // stage the descriptors in a pinned slot and copy them in stream order
-    const int slot = ctx->stage_next;
-    ctx->stage_next = (slot + 1) % gsa_ctx::kStage;
-    if (ctx->stage_used[slot] && (e = hipEventSynchronize(ctx->stage_ev[slot])) != hipSuccess)
-        return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-    if (ctx->stage_cap[slot] < units)
-    {
-        if (ctx->stage[slot]) (void)hipHostFree(ctx->stage[slot]);
-        ctx->stage[slot] = nullptr;
-        ctx->stage_cap[slot] = 0;
-        if ((e = hipHostMalloc((void**)&ctx->stage[slot], units * sizeof(gsa::PairDesc))) != hipSuccess)
-            return fail(ctx, e, GSA_ERROR_MEMORY_ALLOCATION);
-        ctx->stage_cap[slot] = units;
-    }
-    std::memcpy(ctx->stage[slot], hd.data(), (size_t)npairs * sizeof(gsa::PairDesc));
-    if (!sched.empty()) std::memcpy(ctx->stage[slot] + npairs, sched.data(), sched.size() * sizeof(int));
-    e = hipMemcpyAsync(ctx->desc, ctx->stage[slot], units * sizeof(gsa::PairDesc), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->stage_ev[slot], st);
-    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-    ctx->stage_used[slot] = true;
 
     a.pairs = ctx->desc;
     a.nPairs = npairs;
@@ -1900,6 +1917,7 @@ void gsa_ctx_destroy(gsa_ctx* ctx)
     if (ctx->tlist) (void)hipFree(ctx->tlist);
     if (ctx->sbnd) (void)hipFree(ctx->sbnd);
     if (ctx->sctl) (void)hipFree(ctx->sctl);
+    if (ctx->sbatch) (void)hipFree(ctx->sbatch);
     if (ctx->ptflags) (void)hipHostFree(ctx->ptflags);
     if (ctx->ptpin) (void)hipHostFree(ctx->ptpin);
     for (hipEvent_t ev : ctx->ptev)
@@ -2601,6 +2619,28 @@ long long subst_absmax(const int32_t* sub, int32_t substsz)
     return smax;
 }
 
+// Value ranges of one pair (R, C >= 1), smax the largest |substitution value|, which bounds every
+// score and shifted value: errorInvalidValue when no kernel holds the pair; *stripOk: the strip /
+// K-rows score kernels do (else the row scan).
+int score_ranges(int64_t R, int64_t C, long long smax, int32_t gapo, int32_t gape, int32_t local, bool* stripOk)
+{
+    const long long span = (R + C) * (long long)(-gape) + (long long)(gape - gapo) + smax;
+    // unshifted int32 (row scan): |H| <= smax*min(R,C) + |go| + (R+C)|ge|
+    if (smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= (1ll << 30))
+        return GSA_ERROR_INVALID_VALUE;
+    const int bits = sw_idx_bits(R, C);
+    const long long scoreBound = std::min<long long>((1ll << 31) - 1, smax * std::min(R, C));
+    const int scoreBits = scoreBound > 0 ? 64 - __builtin_clzll((unsigned long long)scoreBound) : 1;
+    // SW end-cell keys (score << bits | ~index) must fit 64 bits: the row scan packs full scores
+    if (local && bits + scoreBits > 63) return GSA_ERROR_INVALID_VALUE;
+    // the strip kernel's SW mode needs go < 0 (cells past C then never tie the maximum) and scores
+    // below 2^26 packed with bits index bits (it reports larger ones); both modes keep shifted
+    // values (i+j)*ge apart within int32 with margin; otherwise the row scan
+    // (and scores below 2^26 by construction, so that no shifted key can wrap before the kernel flags it)
+    *stripOk = (!local || (gapo < 0 && bits + 27 <= 63 && smax * std::min(R, C) < (1ll << 26))) && span < (1ll << 28);
+    return GSA_SUCCESS;
+}
+
 // gsa_score_dev; smax < 0: read the table back from the device (in stream order, so the caller's
 // writes to it are seen) to find the largest |value|; gsa_score passes it from its host copy.
 int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
@@ -2633,20 +2673,8 @@ int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int
             return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
         smax = subst_absmax(sub.data(), substsz);
     }
-    const long long span = (R + C) * (long long)(-gape) + (long long)(gape - gapo) + smax;
-    // unshifted int32 (row scan): |H| <= smax*min(R,C) + |go| + (R+C)|ge|
-    if (smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= (1ll << 30))
-        return GSA_ERROR_INVALID_VALUE;
-    const int bits = sw_idx_bits(R, C);
-    const long long scoreBound = std::min<long long>((1ll << 31) - 1, smax * std::min(R, C));
-    const int scoreBits = scoreBound > 0 ? 64 - __builtin_clzll((unsigned long long)scoreBound) : 1;
-    // SW end-cell keys (score << bits | ~index) must fit 64 bits: the row scan packs full scores
-    if (local && bits + scoreBits > 63) return GSA_ERROR_INVALID_VALUE;
-    // the strip kernel's SW mode needs go < 0 (cells past C then never tie the maximum) and scores
-    // below 2^26 packed with bits index bits (it reports larger ones); both modes keep shifted
-    // values (i+j)*ge apart within int32 with margin; otherwise the row scan
-    // (and scores below 2^26 by construction, so that no shifted key can wrap before the kernel flags it)
-    const bool stripOk = (!local || (gapo < 0 && bits + 27 <= 63 && smax * std::min(R, C) < (1ll << 26))) && span < (1ll << 28);
+    bool stripOk = false;
+    if ((s = score_ranges(R, C, smax, gapo, gape, local, &stripOk)) != GSA_SUCCESS) return s;
     if (!score_scan_forced(ctx) && stripOk)
     {
         s = score_ag_strip(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, local, out, st);
@@ -2720,9 +2748,220 @@ int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int
     return GSA_SUCCESS;
 }
 
+// gsa_score_batch_dev: the pairs the K-rows score kernel holds in one persistent launch (their
+// tickets in one ticket space, two result words per pair, decoded on the device), the others -- and
+// those the kernel flags -- one by one through score_dev_impl.
+int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_ms, hipStream_t st)
+{
+    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+    if (batch_ms) *batch_ms = 0.f;
+    // empty pairs: one boundary, nothing to fill (score_dev_impl)
+    std::vector<int> work;
+    for (int p = 0; p < npairs; ++p)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        out[p].calc_kernel_ms = 0.f;
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            out[p].score = (local || k == 0) ? 0 : (int32_t)(gapo + (k - 1) * gape);
+            out[p].i_end = local ? 0 : R;
+            out[p].j_end = local ? 0 : C;
+        }
+        else
+            work.push_back(p);
+    }
+    // the K-rows score kernel, under score_ag_strip's conditions for it (else every pair alone)
+    const bool krow = !score_scan_forced(ctx) && score_kernel_krow(ctx) && gsa::krow_score_lds_bytes(substsz) <= ctx->lds_max;
+    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
+    // rows per lane: 4 in every mode.  A single pair's rule (score_ag_strip: 2 for SW and affine gaps)
+    // shortens its critical path; a batch fills the chip either way, and the longer strip's smaller
+    // share of hand-off wins: 512 pairs of 18-22k, SW-LG 62.5 -> 47.6 ms, NW-AG 68.4 -> 49.7 ms,
+    // NW-LG 54.1 -> 29.3 ms (profiles/score_batch_ab.txt).  GSA_SCORE_K = 2 / 4 forces one
+    const int scoreK = kenv == 2 ? 2 : 4;
+    if (work.empty())
+    {
+        if (krow)
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, 0);  // nothing to launch
+            li.ns = gsa::kSparseNS;
+            li.k = scoreK;
+            li.npairs = npairs;
+        }
+        return GSA_SUCCESS;
+    }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax;
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+    }
+    // the batch's pairs (bp: indices into pairs) and those that run alone
+    const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
+    std::vector<int> bp, alone;
+    std::vector<gsa::PairDesc> hd;
+    long long tickets = 0, gran = 0;
+    for (int p : work)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        bool stripOk = false;
+        int s = score_ranges(R, C, smax, gapo, gape, local, &stripOk);
+        if (s != GSA_SUCCESS) return s;
+        if (!krow || !stripOk)
+        {
+            alone.push_back(p);
+            continue;
+        }
+        gsa::PairDesc d;
+        std::memset(&d, 0, sizeof(d));
+        d.seqY = pairs[p].seqY;
+        d.seqX = pairs[p].seqX;
+        d.R = (int)R;
+        d.C = (int)C;
+        d.Cp = (int)C;
+        d.nTickets = (int)((R + TR - 1) / TR);
+        d.ticketBase = (int)tickets;
+        d.granOff = gran;
+        tickets += d.nTickets;
+        gran += (long long)d.nTickets * gsa::gran_stride(d.Cp);
+        if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+        bp.push_back(p);
+        hd.push_back(d);
+    }
+    float ms = 0.f;
+    if (!bp.empty())
+    {
+        const int nb = (int)bp.size();
+        const std::vector<int> sched = batch_schedule(ctx, hd, tickets);
+        int s = stage_descs(ctx, hd, sched, st);
+        if (s != GSA_SUCCESS) return s;
+        if ((s = ensure_gran(ctx, 2 * (size_t)gran, st)) != GSA_SUCCESS) return s;
+        if (!ctx->sctl && (e = hipMalloc(&ctx->sctl, 64)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_ALLOCATION);
+        // two result words per pair, then the decoded answers and the error word's
+        const size_t resBytes = (size_t)nb * 2 * sizeof(unsigned long long);
+        const size_t outBytes = ((size_t)nb + 1) * sizeof(gsa::ScoreOut);
+        if (ctx->sbatch_cap < resBytes + outBytes)
+        {
+            if (ctx->sbatch) (void)hipFree(ctx->sbatch);
+            ctx->sbatch = nullptr;
+            ctx->sbatch_cap = 0;
+            const size_t cap = std::max<size_t>(resBytes + outBytes, 4096);
+            if ((e = hipMalloc(&ctx->sbatch, cap)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_ALLOCATION);
+            ctx->sbatch_cap = cap;
+        }
+        unsigned long long* const res = (unsigned long long*)ctx->sbatch;
+        gsa::ScoreOut* const dout = (gsa::ScoreOut*)((char*)ctx->sbatch + resBytes);
+        gsa::StripArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.subst = subst;
+        a.substsz = substsz;
+        a.g = gapo;
+        a.go = gapo;
+        a.ge = gape;
+        a.ns = gsa::kSparseNS;
+        a.pairs = ctx->desc;
+        a.nPairs = nb;
+        a.nTicketsTotal = (int)tickets;
+        a.sched = sched.empty() ? nullptr : (const int*)(ctx->desc + nb);
+        a.gran = ctx->gran;
+        a.gran2 = ctx->gran + gran;
+        a.ticket = ctx->ctl;
+        a.err = (unsigned*)(ctx->sctl + 3);  // the score kernels' own error word (score_ag_strip)
+        a.spin = ctx->spin_ticks;
+        a.swBest = res;  // a batch: the base of the pairs' result words
+        if (nb == 1)
+        {
+            // one pair left: the kernel's single-pair form, its words laid out as a batch's pair 0
+            a.agResult = (int*)res;
+            a.swBest = res + 1;
+            a.idxBits = sw_idx_bits(hd[0].R, hd[0].C);
+        }
+        a.epoch = ++ctx->epoch;
+        if (a.epoch == 0) a.epoch = ++ctx->epoch;
+        if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(ctx->sctl, 0, 32, st)) != hipSuccess ||
+            (e = hipMemsetAsync(res, 0, resBytes, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        (void)hipEventRecord(ctx->ev0, st);
+        const int mode = local ? (gapo == gape ? gsa::kModeScoreSWL : gsa::kModeScoreSW)
+                               : (gapo == gape ? gsa::kModeScoreAGL : gsa::kModeScoreAG);
+        // the int8 column profile for NW-LG only: at 4 rows per lane it gains there (512 pairs: 31.5 ->
+        // 29.1 ms), costs NW-AG (49.5 -> 54.3 ms) and leaves SW-LG where it is (47.3 / 47.2;
+        // profiles/score_batch_ab.txt).  GSA_KROW_Q8=0 / 2: int16 / int8 always
+        const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+        a.q8 = (q8env != 0 && (q8env == 2 || mode == gsa::kModeScoreAGL) &&
+                gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+        a.q8flag = ctx->ctl + 2;
+        // one pair: one workgroup per CU (its tickets are a chain); a batch: all resident slots
+        const int grid = nb == 1 ? std::max(1, std::min((int)tickets, ctx->cu_count)) : 0;
+        if ((e = gsa::launch_krow_score(a, mode, scoreK, grid, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        if ((e = gsa::launch_score_finalize(ctx->desc, nb, res, a.err, local != 0, dout, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, a.epoch);
+            li.ns = a.ns;
+            li.k = scoreK;
+            li.q8 = a.q8;
+            li.npairs = npairs;
+            li.pair_major = (nb > 1 && sched.empty()) ? 1 : 0;
+            li.tickets = tickets;
+        }
+        (void)hipEventRecord(ctx->ev1, st);
+        std::vector<gsa::ScoreOut> ho((size_t)nb + 1);
+        if ((e = hipMemcpyAsync(ho.data(), dout, outBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+        const unsigned err = (unsigned)ho[(size_t)nb].score;
+        if (err != 0 && err != 2u) return GSA_ERROR_KERNEL_FAILURE;
+        for (int i = 0; i < nb; ++i)
+        {
+            const gsa::ScoreOut& o = ho[(size_t)i];
+            // a table outside int16 after the shift (every pair), or a pair's score >= 2^26: alone
+            if (err == 2u || o.status != 0)
+            {
+                alone.push_back(bp[(size_t)i]);
+                continue;
+            }
+            gsa_score_result& r = out[bp[(size_t)i]];
+            r.score = o.score;
+            r.i_end = o.i_end;
+            r.j_end = o.j_end;
+        }
+    }
+    for (int p : alone)
+    {
+        int s = score_dev_impl(ctx, pairs[p].seqY, pairs[p].adjrows, pairs[p].seqX, pairs[p].adjcols, subst, substsz, gapo,
+                               gape, local, &out[p], st, smax);
+        if (s != GSA_SUCCESS) return s;
+        ms += out[p].calc_kernel_ms;
+        out[p].calc_kernel_ms = 0.f;
+    }
+    if (batch_ms) *batch_ms = ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                        int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_kernel_ms,
+                        void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, local, out, batch_kernel_ms,
+                            pick_stream(ctx, stream));
+}
 
 int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,

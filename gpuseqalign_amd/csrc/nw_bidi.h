@@ -37,4 +37,12 @@ hipError_t launch_bidi_combine(const int* topH, const int* topF, int ts, const i
                                int m, int mb, int C, int go, int ge, bool affine, int* out, hipStream_t stream,
                                bool local = false);
 
+// Behind a score batch (launch_krow_score with a schedule or several independent pairs): out[p] =
+// pair p's score and end cell decoded from its two result words res[2p], res[2p + 1] (global: the
+// result cell and (R, C); local: the key unpacked with the pair's own sw_idx_bits and C + 1, status
+// 1 when the pair's "score >= 2^26" bit is set), p < nPairs; out[nPairs].score = err[0], so the host
+// reads answers and error word with one copy.
+hipError_t launch_score_finalize(const PairDesc* pairs, int nPairs, const unsigned long long* res, const unsigned* err,
+                                 bool local, ScoreOut* out, hipStream_t stream);
+
 }  // namespace gsa

@@ -103,7 +103,48 @@ __global__ void __launch_bounds__(256) bidi_seed_kernel(const unsigned long long
     }
 }
 
+// score batch: decode pair p's result words (StripArgs::swBest of a batch) into out[p]; out[nPairs]
+// carries the launch's error word
+__global__ void __launch_bounds__(256) score_finalize_kernel(const PairDesc* pairs, int nPairs,
+                                                             const unsigned long long* res, const unsigned* err,
+                                                             int local, ScoreOut* out)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p == nPairs) out[p] = ScoreOut {(int)err[0], 0, 0, 0};
+    if (p >= nPairs) return;
+    const long long R = pairs[p].R, C = pairs[p].C;
+    const unsigned long long w0 = res[2 * (size_t)p], key = res[2 * (size_t)p + 1];
+    ScoreOut o;
+    if (local)
+    {
+        // max key: score << bits | (2^bits-1 - row-major index); 0 = no positive cell -> (0, 0, 0)
+        const int bits = sw_idx_bits(R, C);
+        const unsigned long long mask = (1ull << bits) - 1;
+        const unsigned long long idx = key ? mask - (key & mask) : 0;
+        o.score = (int)(key >> bits);
+        o.i_end = (int)(idx / (unsigned long long)(C + 1));
+        o.j_end = (int)(idx % (unsigned long long)(C + 1));
+        o.status = (int)(w0 & 1u);  // a score >= 2^26
+    }
+    else
+    {
+        o.score = (int)(unsigned)w0;
+        o.i_end = (int)R;
+        o.j_end = (int)C;
+        o.status = 0;
+    }
+    out[p] = o;
+}
+
 }  // namespace
+
+hipError_t launch_score_finalize(const PairDesc* pairs, int nPairs, const unsigned long long* res, const unsigned* err,
+                                 bool local, ScoreOut* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(score_finalize_kernel, dim3((unsigned)(nPairs + 1 + 255) / 256), dim3(256), 0, stream, pairs, nPairs,
+                       res, err, local ? 1 : 0, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_bidi_seed(const unsigned long long* src, const unsigned long long* src2, unsigned long long* dst,
                             unsigned long long* dst2, long long n, unsigned epoch, hipStream_t stream)

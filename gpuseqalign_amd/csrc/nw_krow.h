@@ -47,6 +47,11 @@ hipError_t launch_full_fused(const StripArgs& a, int ns, int waves, bool staged,
 // layout (nw_kscore.hip): 1024-row tickets, grid > 0 workgroups.  Every s - go - ge must lie in
 // (-32768, 32767] (error bit 2 otherwise); SW needs go < 0 and ge <= 0.  a.q8 as launch_kr: the
 // int8-profile instance (values in [-127, 127]) with the int16 one behind it.
+// A batch of independent pairs (a.sched set, or a.nPairs > 1 without a.bidiTop; the BATCH instances):
+// tickets 64 k 4 rows per pair in one ticket space (PairDesc::ticketBase / nTickets / granOff; a.sched:
+// {pair, ticket} per global ticket, ticket j of a pair behind its ticket j-1), a.swBest the base of
+// two result words per pair (nw_strip.h), zeroed by the caller; agResult and idxBits unused; no taps,
+// no bidi fields; grid <= 0: every resident slot.  launch_score_finalize (nw_bidi.h) decodes the words.
 size_t krow_score_lds_bytes(int substsz, bool q8 = false);
 hipError_t launch_krow_score(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
 // (the affine modes' instances, in nw_kscore_ag.hip; called by launch_krow_score)

@@ -2216,8 +2216,11 @@ __device__ __forceinline__ void ks_drain(const StripArgs& a, const KsLds& L, int
 }
 
 // Q8: the int8-profile instance; it declines a table with some s - go - ge outside [-127, 127] as
-// nw_krow_kernel's does (a.q8flag), and the int16 instance behind it (a.q8 = 2) runs only then
-template <int MODE, bool Q8, int K>
+// nw_krow_kernel's does (a.q8flag), and the int16 instance behind it (a.q8 = 2) runs only then.
+// BATCH: the instance for a batch of independent pairs (gsa_score_batch_dev; the launcher picks it,
+// ks_is_batch): an instance of its own, so the single-pair instances keep their code (as a runtime
+// branch of one kernel the mapping cost the 50k pair 1-2 %: SW-LG 2.76 -> 2.83 ms)
+template <int MODE, bool Q8, int K, bool BATCH = false>
 __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_kernel(StripArgs a)
 {
     constexpr int NS = kKrowNSDefault;
@@ -2268,9 +2271,32 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
         const int tkg = __builtin_amdgcn_readfirstlane(lds_ld(L.flags + kFTicket));
         if (tkg >= a.nTicketsTotal) break;
         // one pair (gsa_score), or score_bidi's two (three: local) pairs with their tickets
-        // round-robin while they have some left (each pair's tickets are still claimed in order)
+        // round-robin while they have some left (each pair's tickets are still claimed in order);
+        // BATCH: independent pairs, the schedule's {pair, ticket} or, pair-major, the last
+        // descriptor with ticketBase <= tkg (as nw_krow_kernel)
         int h = 0, tk = tkg + a.tkFirst;
-        if (a.bidiTop > 0)
+        if constexpr (BATCH)
+        {
+            if (a.sched)
+            {
+                h = __builtin_amdgcn_readfirstlane(G(a.sched)[2 * tkg]);
+                tk = __builtin_amdgcn_readfirstlane(G(a.sched)[2 * tkg + 1]);
+            }
+            else
+            {
+                int hi = a.nPairs - 1;
+                while (h < hi)
+                {
+                    const int mid = (h + hi + 1) >> 1;
+                    if (__builtin_amdgcn_readfirstlane(G(a.pairs)[mid].ticketBase) <= tkg)
+                        h = mid;
+                    else
+                        hi = mid - 1;
+                }
+                tk = tkg - __builtin_amdgcn_readfirstlane(G(a.pairs)[h].ticketBase);
+            }
+        }
+        else if (a.bidiTop > 0)
         {
             const int n0 = a.bidiTop, n1 = a.bidiMid > 0 ? a.bidiMid : a.nTicketsTotal - n0;
             const int n2 = a.bidiMid > 0 ? a.nTicketsTotal - n0 - n1 : 0;
@@ -2301,7 +2327,16 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
         pa.tapGran = (a.tapGran >> h) & 1;
         pa.rowOff = d.rowOff;
         if (d.swBest) pa.swBest = d.swBest;
-        if (h == 1)
+        if constexpr (BATCH)
+        {
+            // the pair's own result words and key packing; no taps in a batch
+            pa.agResult = (int*)(a.swBest + 2 * (size_t)h);
+            pa.swBest = a.swBest + 2 * (size_t)h + 1;
+            pa.idxBits = sw_idx_bits(d.R, d.C);
+            pa.tapRow = 0;
+            pa.tapGran = 0;
+        }
+        else if (h == 1)
         {
             pa.tapRow = a.tapRowB;
             pa.tapH = a.tapH + a.tapStride;
@@ -2334,29 +2369,49 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
     }
 }
 
-template <int MODE, bool Q8, int K>
+// a batch of independent pairs (the BATCH instances): a schedule, or several pairs that are not
+// score_bidi's halves
+inline bool ks_is_batch(const StripArgs& a) { return a.sched != nullptr || (a.nPairs > 1 && a.bidiTop == 0); }
+
+template <int MODE, bool Q8, int K, bool BATCH>
 hipError_t launch_ks1(const StripArgs& a, int grid, hipStream_t stream, bool foot)
 {
     const size_t lds = krow_score_lds_bytes(a.substsz, Q8);
-    auto kern = nw_kscore_kernel<MODE, Q8, K>;
+    auto kern = nw_kscore_kernel<MODE, Q8, K, BATCH>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     constexpr int kThreads = 64 * kr_waves<kKrowNSDefault>();
+    if (grid <= 0)
+    {
+        // (a batch) every resident slot, as launch_kr1
+        int per_cu = 0, dev = 0, cus = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kThreads, lds);
+        if (e == hipSuccess) e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+        grid = std::max(1, std::min(a.nTicketsTotal, std::max(1, per_cu) * cus));
+    }
     if (foot && (e = record_foot((const void*)kern, lds, kThreads, grid)) != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, a);
     return hipGetLastError();
 }
 
 // a.q8: the int8 instance, then the int16 one behind it (a no-op unless the int8 launch declined)
-template <int MODE, int K>
-hipError_t launch_ks(const StripArgs& a, int grid, hipStream_t stream)
+template <int MODE, int K, bool BATCH>
+hipError_t launch_ksq(const StripArgs& a, int grid, hipStream_t stream)
 {
-    if (!a.q8) return launch_ks1<MODE, false, K>(a, grid, stream, true);
-    hipError_t e = launch_ks1<MODE, true, K>(a, grid, stream, true);
+    if (!a.q8) return launch_ks1<MODE, false, K, BATCH>(a, grid, stream, true);
+    hipError_t e = launch_ks1<MODE, true, K, BATCH>(a, grid, stream, true);
     if (e != hipSuccess) return e;
     StripArgs b = a;
     b.q8 = 2;
-    return launch_ks1<MODE, false, K>(b, grid, stream, false);
+    return launch_ks1<MODE, false, K, BATCH>(b, grid, stream, false);
+}
+
+template <int MODE, int K>
+hipError_t launch_ks(const StripArgs& a, int grid, hipStream_t stream)
+{
+    return ks_is_batch(a) ? launch_ksq<MODE, K, true>(a, grid, stream) : launch_ksq<MODE, K, false>(a, grid, stream);
 }
 #endif  // GSA_KROW_SCORE
 
@@ -2383,9 +2438,15 @@ size_t krow_score_lds_bytes(int substsz, bool q8) { return (size_t)ks_layout(sub
 
 hipError_t launch_krow_score(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)
 {
-    // one pair, or score_bidi's two halves (bidiTop > 0), three with the fresh bottom (bidiMid > 0)
-    if (a.nPairs != (a.bidiTop > 0 ? (a.bidiMid > 0 ? 3 : 2) : 1) || grid <= 0 || (k != 2 && k != 4))
+    // one pair, or score_bidi's two halves (bidiTop > 0), three with the fresh bottom (bidiMid > 0),
+    // or a batch of independent pairs (a schedule, or more than one pair without bidiTop: no taps,
+    // every ticket from the pair's first, result words per pair at a.swBest)
+    const bool batch = ks_is_batch(a);
+    if (batch ? (a.nPairs < 1 || a.bidiTop != 0 || a.bidiMid != 0 || a.tkFirst != 0 || a.tapGran != 0 || !a.swBest)
+              : a.nPairs != (a.bidiTop > 0 ? (a.bidiMid > 0 ? 3 : 2) : 1))
         return hipErrorInvalidValue;
+    // grid <= 0: every resident slot, for a batch only (one pair's tickets are a chain)
+    if ((grid <= 0 && !batch) || (k != 2 && k != 4)) return hipErrorInvalidValue;
     if (mode == kModeScoreAG || mode == kModeScoreSW) return launch_krow_score_affine(a, mode, k, grid, stream);
     if (k == 2)
     {

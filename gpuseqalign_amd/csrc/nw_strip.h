@@ -144,7 +144,25 @@ struct StripArgs
     // its row above in that ticket's predecessor's granules (copied there with this epoch)
     int tkFirst;
 };
+// Score batch (nw_krow.hip nw_kscore_kernel: sched set, or nPairs > 1 without bidiTop): swBest is
+// the base of two result words per pair, pair p's at swBest[2p] (NW: the result cell in the low
+// int; SW: bit 0 = a score >= 2^26) and swBest[2p + 1] (SW: the pair's end-cell key, packed with
+// sw_idx_bits of its own R and C); agResult and idxBits are not read.
 constexpr int kTapPad = 128;  // tap row buffers: columns -kTapPad .. C + 79
+
+// SW end-cell keys: score << bits | (2^bits-1 - row-major index), bits = ceil(log2((R+1)(C+1)))
+__host__ __device__ inline int sw_idx_bits(long long R, long long C)
+{
+    const unsigned long long n = (unsigned long long)(R + 1) * (unsigned long long)(C + 1) - 1;
+    return n ? 64 - __builtin_clzll(n) : 1;
+}
+
+// One pair's answer of a score batch (launch_score_finalize); status 0: done, 1: the kernel flagged
+// the pair as too large for its packing (the host runs it alone)
+struct ScoreOut
+{
+    int score, i_end, j_end, status;
+};
 
 // Resource footprint of the last fill launched from this host thread: what the reference's
 // updateNwAlgPeakMemUsage (nwalign_shared.cpp:5-25) multiplies out -- kernel attributes

@@ -25,7 +25,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["lpt_partition", "synthetic_batch", "PairResult", "ShardReport", "shard_align", "gpu_batch_align"]
+__all__ = ["lpt_partition", "synthetic_batch", "PairResult", "ShardReport", "shard_align", "gpu_batch_align",
+           "gpu_batch_score"]
 
 
 def lpt_partition(weights: Sequence[int], n_parts: int) -> List[List[int]]:
@@ -290,5 +291,41 @@ def gpu_batch_align(device: int = 0, mode: str = "sparse", tileBx: int = 256, re
                                            subst, gapo))
         eng.close()
         return costs, secs
+
+    return run
+
+
+def gpu_batch_score(device: int = 0, gape: Optional[int] = None, local: bool = False, repeats: int = 1,
+                    warmup: int = 0, launch: Optional[dict] = None) -> AlignBatchFn:
+    """The score-only `align_batch` of one rank (Engine.score_batch_dev): the "cost" it returns per
+    pair is the pair's score (global, or local with local=True; gape None: a linear gap, gapo).
+    Inputs are uploaded before the timed region, then the rank's whole share runs as one batch
+    call (one persistent launch; the call is synchronous).  warmup untimed calls, then the mean of
+    `repeats` timed ones.  launch: a dict that receives Engine.last_launch() of the last call."""
+    import torch
+    from . import Engine
+
+    def run(indices, pairs, subst, gapo):
+        if not indices:
+            return [], 0.0
+        dev = torch.device("cuda", device)
+        substsz = int(round(np.sqrt(subst.size)))
+        eng = Engine(device)
+        ts = torch.from_numpy(np.ascontiguousarray(subst, dtype=np.int32).ravel()).to(dev)
+        ins = [(torch.from_numpy(np.ascontiguousarray(pairs[i][0], dtype=np.int32)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(pairs[i][1], dtype=np.int32)).to(dev)) for i in indices]
+        ptrs = [(y.data_ptr(), len(y), x.data_ptr(), len(x)) for y, x in ins]
+        res = []
+        for _ in range(max(0, warmup)):
+            eng.score_batch_dev(ptrs, ts.data_ptr(), substsz, gapo, gape, local)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(max(1, repeats)):
+            res = eng.score_batch_dev(ptrs, ts.data_ptr(), substsz, gapo, gape, local)
+        secs = (time.perf_counter() - t0) / max(1, repeats)
+        if launch is not None:
+            launch.update(eng.last_launch())
+        eng.close()
+        return [r["score"] for r in res], secs
 
     return run

@@ -358,6 +358,31 @@ typedef struct gsa_score_result
 int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
                   gsa_score_result* out, void* stream);
+/* Many pairs in ONE persistent launch: `pairs` is a host array of `npairs` entries of which only
+ * seqY, adjrows, seqX and adjcols are read (device pointers, as gsa_score_dev's; two entries may
+ * name the same sequences), `out` a host array of `npairs` results.  out[p] is what gsa_score_dev
+ * returns for pair p alone -- score, and end cell with the same first-in-row-major tie rule --
+ * except that out[p].calc_kernel_ms is 0; *batch_kernel_ms (may be null) gets the hipEvent time of
+ * the whole call's kernels.  Synchronous, like gsa_score_dev: the results are in `out` on return.
+ * Every pair gets tickets of 64 K x 4 rows of the K-rows score kernel (K = 4 rows per lane in every
+ * mode, the measured winner for throughput; GSA_SCORE_K = 2 / 4 forces it), the tickets of all pairs run round-robin, longest pair first, as the
+ * batched fills' do (GSA_BATCH_ORDER=pair: pair by pair), and a small kernel behind the fill
+ * decodes every pair's result words, which the host reads with one copy.  No pair is split in two
+ * halves here: the other pairs keep the chip busy.  A pair with an empty sequence is answered on the
+ * host.  Fallback rule -- the results never depend on the path a pair took: a pair outside the
+ * kernel's value range (gsa_score_dev's own test, per pair), or one the kernel reports as too large
+ * (a local score >= 2^26), runs through gsa_score_dev's single-pair path after the batch launch;
+ * the whole batch takes that path, pair by pair, when the kernel reports a table outside int16,
+ * when its profile does not fit LDS, or with GSA_SCORE_SCAN=1 or GSA_SCORE_KERNEL=strip.
+ * gapo > gape, gape > 0, npairs < 1, a null pointer or an entry with adjrows or adjcols < 1 is
+ * errorInvalidValue before anything is enqueued.  The kernel's errors go to the score kernels' own
+ * control word, as gsa_score_dev's.  gsa_last_launch then reports the batch launch (kind
+ * GSA_LAUNCH_SCORE_KROW, npairs as passed, the tickets of all pairs, k, q8, pair_major), or the
+ * last single-pair launch when a pair took the fallback.
+ * Pairs much shorter than a ticket leave most of its lanes idle. */
+int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                        int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
+                        float* batch_kernel_ms, void* stream);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
