@@ -110,7 +110,7 @@ class LaunchInfo(ctypes.Structure):
 
 # enum gsa_launch_kind (include/gsa.h), by value
 LAUNCH_KINDS = ("none", "full_lane", "full_fused", "full_two_launch", "sparse_krow", "sparse_strip", "score_krow",
-                "score_strip", "score_scan", "trace_sparse")
+                "score_strip", "score_scan", "trace_sparse", "score_lanes")
 
 
 class ScoreResult(ctypes.Structure):
@@ -183,6 +183,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ScoreResult), _vp]),
     "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
+                                        ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score": (ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -197,7 +199,8 @@ KNOB_NAMES = (
     "GSA_FUSED_STAGED",
     "GSA_EXPAND_RR", "GSA_BATCH_ORDER", "GSA_SCORE_SCAN", "GSA_SCORE_KERNEL", "GSA_SCORE_K",
     "GSA_SCORE_BIDI", "GSA_SCORE_BIDI_SW", "GSA_BIDI_GRAN", "GSA_BIDI_SKEW", "GSA_BIDI_SW_CONT",
-    "GSA_BIDI_LOG", "GSA_TRACE_BAND", "GSA_TRACE_BAND_BUDGET", "GSA_STAMPS")
+    "GSA_BIDI_LOG", "GSA_TRACE_BAND", "GSA_TRACE_BAND_BUDGET", "GSA_STAMPS", "GSA_DB_LANES",
+    "GSA_DB_MAXC")
 
 
 def lib():
@@ -513,6 +516,43 @@ class Engine:
             ptrs.append((dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel()))
         torch.cuda.synchronize(dev)
         return self.score_batch_dev(ptrs, dS.data_ptr(), substsz, gapo, gape, local)
+
+    def score_db_dev(self, query_ptr: int, adjq: int, db_ptr: int, db_off, subst_ptr: int, substsz: int, gapo: int,
+                     gape: Optional[int] = None, local: bool = False, stream: Optional[int] = None) -> list:
+        """Database search (gsa_score_db_dev; synchronous): one device-resident query against the
+        subjects of one device buffer `db_ptr`, each with its header element; `db_off` holds the
+        len(db_off) - 1 subjects' offsets into it (ints, strictly increasing).  One dict per subject,
+        equal to score_dev's for (query, subject) except "kernel_ms", the hipEvent time of the whole
+        call's kernels in every dict."""
+        off = np.ascontiguousarray(db_off, dtype=np.int64)
+        n = len(off) - 1
+        res = (ScoreResult * max(n, 1))()
+        ms = ctypes.c_float(0.0)
+        st = lib().gsa_score_db_dev(self._h, query_ptr, adjq, db_ptr, off.ctypes.data_as(ctypes.POINTER(_i64)), n,
+                                    subst_ptr, substsz, gapo, gapo if gape is None else gape, int(local), res,
+                                    ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_db_dev")
+        return [{"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end), "kernel_ms": float(ms.value)}
+                for r in res[:n]]
+
+    def score_db(self, query, subjects, subst, gapo: int, gape: Optional[int] = None, local: bool = False) -> list:
+        """score_db_dev over host arrays: `query` and every entry of `subjects` with the header
+        element in front, as score() takes them.  The subjects are concatenated and uploaded once
+        through torch.  One dict per subject: {"score", "i_end", "j_end", "kernel_ms"}."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        subjects = [_c32(x) for x in subjects]
+        off = np.zeros(len(subjects) + 1, dtype=np.int64)
+        if subjects:
+            off[1:] = np.cumsum([len(x) for x in subjects])
+        dS, dQ = up(subst.ravel()), up(query)
+        dD = up(np.concatenate(subjects) if subjects else np.zeros(1, np.int32))
+        torch.cuda.synchronize(dev)
+        return self.score_db_dev(dQ.data_ptr(), dQ.numel(), dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
+                                 local)
 
     # -- device-side verification (SURVEY.md 8(f)1) ---------------------------------------
 

@@ -23,6 +23,7 @@
 #include "nw_bidi.h"
 #include "nw_check.h"
 #include "nw_lane.h"
+#include "nw_lanes.h"
 #include "nw_expand.h"
 #include "nw_krow.h"
 #include "nw_strip.h"
@@ -155,6 +156,12 @@ struct gsa_ctx
     // (gsa::ScoreOut per pair and one for the error word); grow-only
     void* sbatch = nullptr;
     size_t sbatch_cap = 0;  // bytes
+    // database search (gsa_score_db_dev): task counter, the lane subjects' offsets, lengths and results;
+    // the boundary rows of the resident waves (queries of more than one sweep); grow-only
+    void* dbl = nullptr;
+    size_t dbl_cap = 0;  // bytes
+    void* dbbnd = nullptr;
+    size_t dbbnd_cap = 0;  // bytes
     // copy-back of the host-buffer entry points into pageable caller memory: per copy thread a
     // stream and two pinned chunks (DMA of chunk k+1 overlaps the host copy of chunk k)
     static constexpr int kCopyThreads = 8;
@@ -258,7 +265,8 @@ constexpr const char* kKnobNames[] = {
     "GSA_FUSED_STAGED",
     "GSA_EXPAND_RR",     "GSA_BATCH_ORDER", "GSA_SCORE_SCAN",   "GSA_SCORE_KERNEL",  "GSA_SCORE_K",
     "GSA_SCORE_BIDI",    "GSA_SCORE_BIDI_SW", "GSA_BIDI_GRAN",  "GSA_BIDI_SKEW",     "GSA_BIDI_SW_CONT",
-    "GSA_BIDI_LOG",      "GSA_TRACE_BAND",  "GSA_TRACE_BAND_BUDGET", "GSA_STAMPS"};
+    "GSA_BIDI_LOG",      "GSA_TRACE_BAND",  "GSA_TRACE_BAND_BUDGET", "GSA_STAMPS",     "GSA_DB_LANES",
+    "GSA_DB_MAXC"};
 
 bool knob_known(const char* name)
 {
@@ -317,7 +325,7 @@ long long held_bytes(const gsa_ctx* c)
                   (long long)c->tband_cap + (long long)c->tlist_cap * 4 + (long long)c->excap +
                   (long long)c->exdesc_cap + (long long)c->excap2 + (long long)c->exdesc_cap2 +
                   8 * (long long)(c->xdone_cap + c->stamps_cap + c->clk_cap) +
-                  4 * (long long)c->bidi_cap + (long long)c->sbatch_cap;
+                  4 * (long long)c->bidi_cap + (long long)c->sbatch_cap + (long long)c->dbl_cap + (long long)c->dbbnd_cap;
     for (size_t k : c->dcap) b += (long long)k;
     return b;
 }
@@ -1918,6 +1926,8 @@ void gsa_ctx_destroy(gsa_ctx* ctx)
     if (ctx->sbnd) (void)hipFree(ctx->sbnd);
     if (ctx->sctl) (void)hipFree(ctx->sctl);
     if (ctx->sbatch) (void)hipFree(ctx->sbatch);
+    if (ctx->dbl) (void)hipFree(ctx->dbl);
+    if (ctx->dbbnd) (void)hipFree(ctx->dbbnd);
     if (ctx->ptflags) (void)hipHostFree(ctx->ptflags);
     if (ctx->ptpin) (void)hipHostFree(ctx->ptpin);
     for (hipEvent_t ev : ctx->ptev)
@@ -2950,6 +2960,195 @@ int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
     return GSA_SUCCESS;
 }
 
+// Longest subject the database search sends to the lane kernel (GSA_DB_MAXC overrides it): the largest
+// length of the sweep of tools/score_db_bench.py at which that kernel still beat the batched K-rows
+// path in all three modes (profiles/score_db_ab.txt).  Measured: it won at every swept
+// length, 64 ... 4096 (1.4-1.9x), so this is the sweep's upper end, not a crossover.
+constexpr int kDbLanesLmax = 4096;
+
+int ensure_bytes(gsa_ctx* ctx, void** buf, size_t* cap, size_t bytes)
+{
+    if (*cap >= bytes && *buf) return GSA_SUCCESS;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const size_t want = std::max<size_t>(bytes, 4096);
+    hipError_t e = hipMalloc(buf, want);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_ALLOCATION);
+    *cap = want;
+    return GSA_SUCCESS;
+}
+
+// gsa_score_db_dev: empty pairs on the host, the subjects the lane kernel does not take through
+// score_batch_impl (first, so that gsa_last_launch reports the lane launch), the others, longest
+// first, four to a wave task in one launch of nw_lanes.hip.
+int score_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                  int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                  gsa_score_result* out, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !query || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    if (nsubj < 1 || adjq < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (db_off[0] < 0) return GSA_ERROR_INVALID_VALUE;
+    for (int s = 0; s < nsubj; ++s)
+        if (db_off[s + 1] <= db_off[s] || db_off[s + 1] - db_off[s] > (int64_t)INT32_MAX) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    auto pair_of = [&](int s) {
+        gsa_pair_dev p;
+        std::memset(&p, 0, sizeof(p));
+        p.seqY = query;
+        p.adjrows = adjq;
+        p.seqX = db + db_off[s];
+        p.adjcols = (int32_t)(db_off[s + 1] - db_off[s]);
+        return p;
+    };
+    if (env_int(ctx, "GSA_DB_LANES", 1) == 0)
+    {
+        std::vector<gsa_pair_dev> pairs((size_t)nsubj);
+        for (int s = 0; s < nsubj; ++s) pairs[(size_t)s] = pair_of(s);
+        return score_batch_impl(ctx, nsubj, pairs.data(), subst, substsz, gapo, gape, local, out, kernel_ms, st);
+    }
+    const int64_t R = adjq - 1;
+    // empty pairs: one boundary, nothing to fill (score_batch_impl's rule)
+    std::vector<int> work;
+    for (int s = 0; s < nsubj; ++s)
+    {
+        const int64_t C = db_off[s + 1] - db_off[s] - 1;
+        out[s].calc_kernel_ms = 0.f;
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            out[s].score = (local || k == 0) ? 0 : (int32_t)(gapo + (k - 1) * gape);
+            out[s].i_end = local ? 0 : R;
+            out[s].j_end = local ? 0 : C;
+        }
+        else
+            work.push_back(s);
+    }
+    if (work.empty()) return GSA_SUCCESS;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax;
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+    }
+    const int lmax = std::max(0, std::min(env_int(ctx, "GSA_DB_MAXC", kDbLanesLmax), gsa::kDbLanesMaxC));
+    // the query's profile must fit LDS (else every subject takes the other path)
+    const bool fits = R < (1 << 20) && gsa::dblanes_lds_bytes((int)R, substsz) <= (size_t)ctx->lds_max;
+    std::vector<int> lanes, other;
+    for (int s : work)
+    {
+        const int64_t C = db_off[s + 1] - db_off[s] - 1;
+        bool stripOk = false;
+        int st2 = score_ranges(R, C, smax, gapo, gape, local, &stripOk);
+        if (st2 != GSA_SUCCESS) return st2;
+        // local: a row's best key packs the score above 13 column bits
+        const bool keyOk = !local || smax * std::min(R, C) < gsa::kDbLanesMaxScore;
+        (fits && C <= lmax && keyOk ? lanes : other).push_back(s);
+    }
+    float ms = 0.f;
+    if (!other.empty())
+    {
+        std::vector<gsa_pair_dev> pairs(other.size());
+        std::vector<gsa_score_result> res(other.size());
+        for (size_t k = 0; k < other.size(); ++k) pairs[k] = pair_of(other[k]);
+        int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local, res.data(),
+                                 &ms, st);
+        if (s != GSA_SUCCESS) return s;
+        for (size_t k = 0; k < other.size(); ++k) out[other[k]] = res[k];
+    }
+    if (!lanes.empty())
+    {
+        // longest first: a task's four subjects are of like length, and the long tasks start first
+        std::stable_sort(lanes.begin(), lanes.end(), [&](int x, int y) {
+            return db_off[x + 1] - db_off[x] > db_off[y + 1] - db_off[y];
+        });
+        const size_t n = lanes.size();
+        const int ntasks = (int)((n + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+        const int cmax = (int)(db_off[lanes[0] + 1] - db_off[lanes[0]] - 1);
+        const int passes = (int)((R + gsa::kDbLanesPassRows - 1) / gsa::kDbLanesPassRows);
+        std::vector<long long> hoff(n);
+        std::vector<int> hlen(n);
+        for (size_t k = 0; k < n; ++k)
+        {
+            hoff[k] = (long long)db_off[lanes[k]];
+            hlen[k] = (int)(db_off[lanes[k] + 1] - db_off[lanes[k]] - 1);
+        }
+        // [counter, 64 B][offsets][lengths][results]
+        const size_t offAt = 64, lenAt = offAt + n * 8, outAt = (lenAt + n * 4 + 15) / 16 * 16;
+        const size_t bytes = outAt + n * sizeof(gsa::DbLanesOut);
+        int s = ensure_bytes(ctx, &ctx->dbl, &ctx->dbl_cap, bytes);
+        if (s != GSA_SUCCESS) return s;
+        int wgs = 1;
+        if ((e = gsa::dblanes_resident((int)R, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        const int grid = std::max(1, std::min(wgs, (ntasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+        const int bndStride = cmax + 1;
+        if (passes > 1)
+        {
+            // per resident wave and subject slot, (H, F) by column: bounded by the waves, not the database
+            const size_t bb = (size_t)grid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)bndStride * sizeof(int2);
+            if ((s = ensure_bytes(ctx, &ctx->dbbnd, &ctx->dbbnd_cap, bb)) != GSA_SUCCESS) return s;
+        }
+        char* const base = (char*)ctx->dbl;
+        gsa::DbLanesArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.query = query;
+        a.db = db;
+        a.subst = subst;
+        a.substsz = substsz;
+        a.go = gapo;
+        a.ge = gape;
+        a.R = (int)R;
+        a.passes = passes;
+        a.nsubj = (int)n;
+        a.ntasks = ntasks;
+        a.off = (const long long*)(base + offAt);
+        a.len = (const int*)(base + lenAt);
+        a.out = (gsa::DbLanesOut*)(base + outAt);
+        a.counter = (unsigned*)base;
+        a.bnd = passes > 1 ? (int2*)ctx->dbbnd : nullptr;
+        a.bndStride = bndStride;
+        if ((e = hipMemsetAsync(base, 0, 64, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(base + offAt, hoff.data(), n * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(base + lenAt, hlen.data(), n * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        (void)hipEventRecord(ctx->ev0, st);
+        if ((e = gsa::launch_dblanes(a, local, grid, nullptr, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventRecord(ctx->ev1, st);
+        note_launch(ctx);
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_LANES, st, 0);
+            li.ns = gsa::kDbLanesWaves;
+            li.k = gsa::kDbLanesKQ;
+            li.npairs = (int32_t)n;
+            li.tickets = ntasks;
+        }
+        std::vector<gsa::DbLanesOut> ho(n);
+        if ((e = hipMemcpyAsync(ho.data(), a.out, n * sizeof(gsa::DbLanesOut), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        float lms = 0.f;
+        (void)hipEventElapsedTime(&lms, ctx->ev0, ctx->ev1);
+        ms += lms;
+        for (size_t k = 0; k < n; ++k)
+        {
+            gsa_score_result& r = out[lanes[k]];
+            r.score = ho[k].score;
+            r.i_end = ho[k].i_end;
+            r.j_end = ho[k].j_end;
+            r.calc_kernel_ms = 0.f;
+        }
+    }
+    if (kernel_ms) *kernel_ms = ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2961,6 +3160,15 @@ int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs,
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return score_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, local, out, batch_kernel_ms,
                             pick_stream(ctx, stream));
+}
+
+int gsa_score_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                     int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                     gsa_score_result* out, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_db_impl(ctx, query, adjq, db, db_off, nsubj, subst, substsz, gapo, gape, local, out, kernel_ms,
+                         pick_stream(ctx, stream));
 }
 
 int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,

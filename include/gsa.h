@@ -233,7 +233,10 @@ enum gsa_launch_kind
     GSA_LAUNCH_SCORE_KROW = 6,      /* K-rows score kernel */
     GSA_LAUNCH_SCORE_STRIP = 7,     /* strip kernel's score modes */
     GSA_LAUNCH_SCORE_SCAN = 8,      /* row scan (nw_scan.hip) */
-    GSA_LAUNCH_TRACE_SPARSE = 9     /* gsa_trace_sparse_dev */
+    GSA_LAUNCH_TRACE_SPARSE = 9,    /* gsa_trace_sparse_dev */
+    GSA_LAUNCH_SCORE_LANES = 10     /* database search, a subject per group of lanes (nw_lanes.hip):
+                                     * npairs = subjects on that kernel, tickets = wave tasks, k = query
+                                     * rows per lane, ns = waves per workgroup */
 };
 typedef struct gsa_launch_info
 {
@@ -383,6 +386,29 @@ int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int3
 int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
                         int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
                         float* batch_kernel_ms, void* stream);
+/* One query against a database of subjects, score-only; semantics of gsa_score_dev with
+ * seqY = query, seqX = subject s.  db is ONE device buffer holding the subjects back to back, each
+ * with its own header element 0 in front; subject s is db + db_off[s], adjcols = db_off[s+1] - db_off[s].
+ * db_off is a HOST array of nsubj + 1 strictly increasing offsets (every subject has at least its
+ * header).  out is a host array of nsubj results: out[s] is exactly what gsa_score_dev returns for
+ * (query, subject s) -- score, and for local the first maximal cell in row-major order -- with
+ * calc_kernel_ms = 0; *kernel_ms (may be null) gets the hipEvent time of the call's kernels.
+ * Synchronous.
+ * Subjects of at most Lmax letters (GSA_DB_MAXC=n overrides it, at most 8191) run on
+ * the lane kernel (nw_lanes.hip): every subject on 16 lanes of a wave, no wave waiting for another.
+ * The results never depend on the path: longer subjects, local pairs whose score bound
+ * (largest |table value| x the shorter length) reaches 2^18, and every subject when the query's
+ * profile does not fit LDS or with GSA_DB_LANES=0 run through gsa_score_batch_dev's path, as a pair
+ * list built inside the call, before the lane launch.  A subject with no letters, or an empty query,
+ * is answered on the host.  A null pointer, nsubj < 1, adjq < 1, an offset that does not increase,
+ * gapo > gape, gape > 0, substsz outside 1..32 or a pair outside every kernel's value range is
+ * errorInvalidValue before anything is enqueued.  The fills' sticky error word is left alone.
+ * gsa_last_launch reports the lane launch (kind GSA_LAUNCH_SCORE_LANES) when any subject took it,
+ * else what the other path reports. */
+int gsa_score_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db,
+                     const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
+                     float* kernel_ms, void* stream);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
