@@ -119,6 +119,20 @@ class ScoreResult(ctypes.Structure):
                 ("calc_kernel_ms", ctypes.c_float)]
 
 
+class AlignDbResult(ctypes.Structure):
+    """gsa_align_db_result (include/gsa.h)."""
+    _fields_ = [("score", ctypes.c_int32), ("status", ctypes.c_int32), ("i_start", ctypes.c_int64),
+                ("j_start", ctypes.c_int64), ("i_end", ctypes.c_int64), ("j_end", ctypes.c_int64),
+                ("cigar_off", ctypes.c_int64), ("cigar_len", ctypes.c_int64)]
+
+
+class AlignDbInfo(ctypes.Structure):
+    """gsa_align_db_info (include/gsa.h): what the last gsa_align_db_dev call ran."""
+    _fields_ = [("lane_hits", ctypes.c_int32), ("unsupported", ctypes.c_int32), ("chunks", ctypes.c_int32),
+                ("tasks", ctypes.c_int64), ("code_bytes", ctypes.c_int64), ("fill_ms", ctypes.c_float),
+                ("walk_ms", ctypes.c_float)]
+
+
 _LAPFN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)  # gsa_lap_fn
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
@@ -185,7 +199,11 @@ SIGNATURES = {
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
                                         ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
-    "gsa_score": (ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
+    "gsa_align_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _i32p, _i32, _vp, _i32, _i32,
+                                        _i32, _i32, _i64, ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                        ctypes.POINTER(_i64), ctypes.POINTER(AlignDbInfo),
+                                        ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score":(ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
                                             _vp, _vp, ctypes.c_char_p, _i64, ctypes.POINTER(ctypes.c_int64),
@@ -553,6 +571,84 @@ class Engine:
         torch.cuda.synchronize(dev)
         return self.score_db_dev(dQ.data_ptr(), dQ.numel(), dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
                                  local)
+
+    # -- alignments of database hits, traced on the device ----------------
+
+    def align_db_dev(self, query_ptr: int, adjq: int, db_ptr: int, db_off, hits, subst_ptr: int, substsz: int,
+                     gapo: int, gape: Optional[int] = None, local: bool = False, scratch_limit: int = 0,
+                     stream: Optional[int] = None) -> list:
+        """The alignments of chosen subjects of a database (gsa_align_db_dev; synchronous): query,
+        database and table as score_db_dev takes them, `hits` the subject indices (any order, repeats
+        allowed), `scratch_limit` the bytes of move codes held at once (0: the default).  One dict per
+        hit, in order: {"score", "status", "i_start", "j_start", "i_end", "j_end", "cigar", "kernel_ms"};
+        status 0 aligned, 1 score and end cell only (outside the trace kernel's limits; "cigar" is "").
+        "kernel_ms" is the hipEvent time of the whole call's kernels in every dict.
+        last_align_db_info() says what the call ran."""
+        off = np.ascontiguousarray(db_off, dtype=np.int64)
+        hit = np.ascontiguousarray(hits, dtype=np.int32).ravel()
+        n, nh = len(off) - 1, len(hit)
+        res = (AlignDbResult * max(nh, 1))()
+        info = AlignDbInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes per hit always suffice
+        cap = 0
+        if nh and n >= 1 and hit.min() >= 0 and hit.max() < n:
+            cap = int(2 * (np.diff(off)[hit].clip(1) - 1 + max(adjq - 1, 0)).sum() + nh)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        st = lib().gsa_align_db_dev(self._h, query_ptr, adjq, db_ptr, off.ctypes.data_as(ctypes.POINTER(_i64)), n,
+                                    hit.ctypes.data_as(_i32p), nh, subst_ptr, substsz, gapo,
+                                    gapo if gape is None else gape, int(local), int(scratch_limit), res, buf, cap,
+                                    ctypes.byref(need), ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_db_dev")
+        self._align_db_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                               for k, t in info._fields_}
+        raw = buf.raw
+        out = []
+        for r in res[:nh]:
+            cig = raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else ""
+            out.append({"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start),
+                        "j_start": int(r.j_start), "i_end": int(r.i_end), "j_end": int(r.j_end), "cigar": cig,
+                        "kernel_ms": float(ms.value)})
+        return out
+
+    def last_align_db_info(self) -> dict:
+        """gsa_align_db_info of the last align_db_dev call on this engine: "lane_hits" traced on the
+        device, "unsupported" (status 1), "chunks" (fill + walk launch pairs), "tasks", "code_bytes"
+        (peak bytes of move codes held at once), "fill_ms" and "walk_ms"."""
+        info = getattr(self, "_align_db_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_db_info: no align_db_dev call yet")
+        return dict(info)
+
+    def align_db(self, query, subjects, hits, subst, gapo: int, gape: Optional[int] = None,
+                 local: bool = False) -> list:
+        """align_db_dev over host arrays: `query` and every entry of `subjects` with the header element
+        in front, as score_db takes them; `hits` indexes `subjects`."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        subjects = [_c32(x) for x in subjects]
+        off = np.zeros(len(subjects) + 1, dtype=np.int64)
+        if subjects:
+            off[1:] = np.cumsum([len(x) for x in subjects])
+        dS, dQ = up(subst.ravel()), up(query)
+        dD = up(np.concatenate(subjects) if subjects else np.zeros(1, np.int32))
+        torch.cuda.synchronize(dev)
+        return self.align_db_dev(dQ.data_ptr(), dQ.numel(), dD.data_ptr(), off, hits, dS.data_ptr(), substsz, gapo,
+                                 gape, local)
+
+    def search_db(self, query, subjects, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
+                  top: int = 10) -> list:
+        """Database search with alignments: score_db over all subjects, then align_db on the `top` best
+        scores (equal scores: the smaller index first).  [(subject_index, result dict)] in that order."""
+        scores = self.score_db(query, subjects, subst, gapo, gape, local)
+        order = sorted(range(len(scores)), key=lambda s: (-scores[s]["score"], s))[:max(int(top), 0)]
+        if not order:
+            return []
+        return list(zip(order, self.align_db(query, subjects, order, subst, gapo, gape, local)))
 
     # -- device-side verification (SURVEY.md 8(f)1) ---------------------------------------
 

@@ -24,6 +24,7 @@
 #include "nw_check.h"
 #include "nw_lane.h"
 #include "nw_lanes.h"
+#include "nw_lanes_trace.h"
 #include "nw_expand.h"
 #include "nw_krow.h"
 #include "nw_strip.h"
@@ -162,6 +163,16 @@ struct gsa_ctx
     size_t dbl_cap = 0;  // bytes
     void* dbbnd = nullptr;
     size_t dbbnd_cap = 0;  // bytes
+    // alignments of database hits (gsa_align_db_dev): the move codes of one chunk, its task counter and
+    // per-hit offsets, lengths and fill results, the walk's results and move bytes; grow-only; the
+    // events around the fill and the walk
+    void* adbcodes = nullptr;
+    size_t adbcodes_cap = 0;  // bytes
+    void* adbmeta = nullptr;
+    size_t adbmeta_cap = 0;  // bytes
+    void* adbres = nullptr;
+    size_t adbres_cap = 0;  // bytes
+    hipEvent_t adbev[3] = {nullptr, nullptr, nullptr};
     // copy-back of the host-buffer entry points into pageable caller memory: per copy thread a
     // stream and two pinned chunks (DMA of chunk k+1 overlaps the host copy of chunk k)
     static constexpr int kCopyThreads = 8;
@@ -325,7 +336,8 @@ long long held_bytes(const gsa_ctx* c)
                   (long long)c->tband_cap + (long long)c->tlist_cap * 4 + (long long)c->excap +
                   (long long)c->exdesc_cap + (long long)c->excap2 + (long long)c->exdesc_cap2 +
                   8 * (long long)(c->xdone_cap + c->stamps_cap + c->clk_cap) +
-                  4 * (long long)c->bidi_cap + (long long)c->sbatch_cap + (long long)c->dbl_cap + (long long)c->dbbnd_cap;
+                  4 * (long long)c->bidi_cap + (long long)c->sbatch_cap + (long long)c->dbl_cap + (long long)c->dbbnd_cap +
+                  (long long)c->adbcodes_cap + (long long)c->adbmeta_cap + (long long)c->adbres_cap;
     for (size_t k : c->dcap) b += (long long)k;
     return b;
 }
@@ -1928,6 +1940,11 @@ void gsa_ctx_destroy(gsa_ctx* ctx)
     if (ctx->sbatch) (void)hipFree(ctx->sbatch);
     if (ctx->dbl) (void)hipFree(ctx->dbl);
     if (ctx->dbbnd) (void)hipFree(ctx->dbbnd);
+    if (ctx->adbcodes) (void)hipFree(ctx->adbcodes);
+    if (ctx->adbmeta) (void)hipFree(ctx->adbmeta);
+    if (ctx->adbres) (void)hipFree(ctx->adbres);
+    for (hipEvent_t ev : ctx->adbev)
+        if (ev) (void)hipEventDestroy(ev);
     if (ctx->ptflags) (void)hipHostFree(ctx->ptflags);
     if (ctx->ptpin) (void)hipHostFree(ctx->ptpin);
     for (hipEvent_t ev : ctx->ptev)
@@ -3149,9 +3166,312 @@ int score_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
     return GSA_SUCCESS;
 }
 
+// Default of gsa_align_db_dev's scratch_limit: bytes of move codes a call holds at once.
+constexpr int64_t kAlignDbScratch = 256ll << 20;
+
+// The move bytes of a walk (last move first) as a CIGAR: forward order, run-length encoded.
+std::string fold_cigar(const unsigned char* mv, int64_t n)
+{
+    std::string s;
+    for (int64_t k = n - 1; k >= 0;)
+    {
+        const unsigned char op = mv[k];
+        int64_t run = 0;
+        while (k >= 0 && mv[k] == op)
+        {
+            ++run;
+            --k;
+        }
+        char dig[24];
+        int nd = 0;
+        for (int64_t v = run; v > 0; v /= 10) dig[nd++] = (char)('0' + v % 10);
+        while (nd > 0) s += dig[--nd];
+        s += (char)op;
+    }
+    return s;
+}
+
+// gsa_align_db_dev: hits with an empty side on the host; the hits the trace kernels take, longest
+// first, in chunks whose move codes fit scratch_limit, a fill and a walk launch per chunk and one copy
+// of the results and move bytes back (nw_lanes_trace.hip); the others (status 1) through
+// score_batch_impl for their score and end cell.  gsa_last_launch's record is left as it was.
+int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                  int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
+                  int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
+                  char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info, float* kernel_ms,
+                  hipStream_t st)
+{
+    if (!ctx || !query || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    if (nsubj < 1 || adjq < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (nhits < 0 || scratch_limit < 0 || cigar_cap < 0) return GSA_ERROR_INVALID_VALUE;
+    if ((nhits > 0 && !hits) || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (db_off[0] < 0) return GSA_ERROR_INVALID_VALUE;
+    for (int s = 0; s < nsubj; ++s)
+        if (db_off[s + 1] <= db_off[s] || db_off[s + 1] - db_off[s] > (int64_t)INT32_MAX) return GSA_ERROR_INVALID_VALUE;
+    for (int h = 0; h < nhits; ++h)
+        if (hits[h] < 0 || hits[h] >= nsubj) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_db_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t R = adjq - 1;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax = 1;
+    if (R > 0)
+    {
+        // gsa_score_db_dev's range test, over the whole database: the same calls are rejected
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+        for (int s = 0; s < nsubj; ++s)
+        {
+            const int64_t C = db_off[s + 1] - db_off[s] - 1;
+            bool stripOk = false;
+            if (C > 0 && score_ranges(R, C, smax, gapo, gape, local, &stripOk) != GSA_SUCCESS)
+                return GSA_ERROR_INVALID_VALUE;
+        }
+    }
+    if (nhits == 0) return GSA_SUCCESS;
+
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : kAlignDbScratch;
+    const bool fits = R < (1 << 20) && gsa::dblanes_lds_bytes((int)R, substsz) <= (size_t)ctx->lds_max;
+    std::vector<std::string> cig((size_t)nhits);
+    std::vector<int> lanes, other;
+    for (int h = 0; h < nhits; ++h)
+    {
+        const int64_t C = db_off[hits[h] + 1] - db_off[hits[h]] - 1;
+        gsa_align_db_result& r = out[h];
+        std::memset(&r, 0, sizeof(r));
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            if (!local && k > 0)
+            {
+                r.score = (int32_t)(gapo + (k - 1) * gape);
+                r.i_end = R;
+                r.j_end = C;
+                cig[(size_t)h] = std::to_string(k) + (R > 0 ? 'I' : 'D');
+            }
+            continue;
+        }
+        const bool keyOk = !local || smax * std::min(R, C) < gsa::kDbLanesMaxScore;
+        // the fill keeps 4 x value + source: |H| <= smax min(R, C) + |go| + (R + C) |ge| (score_ranges' bound)
+        const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+        const bool take = fits && C <= gsa::kDbLanesMaxC && keyOk && valOk && gsa::dbtrace_code_bytes(R, C) <= limit;
+        (take ? lanes : other).push_back(h);
+    }
+    auto len_of = [&](int h) { return db_off[hits[h] + 1] - db_off[hits[h]] - 1; };
+    float fill_ms = 0.f, walk_ms = 0.f, other_ms = 0.f;
+    if (!lanes.empty())
+    {
+        // longest first: a task's four hits are of like length, and the long tasks start first
+        std::stable_sort(lanes.begin(), lanes.end(), [&](int x, int y) { return len_of(x) > len_of(y); });
+        // chunks [first, last) whose codes fit the limit; the largest of every buffer over the chunks
+        std::vector<std::pair<size_t, size_t>> chunks;
+        size_t maxN = 0;
+        int64_t maxCodes = 0, maxMoves = 0;
+        for (size_t b = 0; b < lanes.size();)
+        {
+            size_t k = b;
+            int64_t cb = 0, mb = 0;
+            while (k < lanes.size() && cb + gsa::dbtrace_code_bytes(R, len_of(lanes[k])) <= limit)
+            {
+                cb += gsa::dbtrace_code_bytes(R, len_of(lanes[k]));
+                mb += R + len_of(lanes[k]);
+                ++k;
+            }
+            chunks.emplace_back(b, k);
+            maxN = std::max(maxN, k - b);
+            maxCodes = std::max(maxCodes, cb);
+            maxMoves = std::max(maxMoves, mb);
+            b = k;
+        }
+        const int passes = (int)((R + gsa::kDbLanesPassRows - 1) / gsa::kDbLanesPassRows);
+        const int cmax = (int)len_of(lanes[0]);
+        int wgs = 1;
+        if ((e = gsa::dbtrace_resident((int)R, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        const int maxTasks = (int)((maxN + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+        const int maxGrid = std::max(1, std::min(wgs, (maxTasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+        // meta: [counter, 64 B][offsets][code offsets][move offsets][lengths][fill results]
+        const size_t offAt = 64, coffAt = offAt + maxN * 8, moffAt = coffAt + maxN * 8, lenAt = moffAt + maxN * 8;
+        const size_t foutAt = (lenAt + maxN * 4 + 15) / 16 * 16;
+        const size_t metaBytes = foutAt + maxN * sizeof(gsa::DbLanesOut);
+        // results: [walk results][move bytes]
+        const size_t movAt = maxN * sizeof(gsa::DbTraceOut);
+        const size_t resBytes = movAt + (size_t)maxMoves;
+        int s;
+        if ((s = ensure_bytes(ctx, &ctx->adbmeta, &ctx->adbmeta_cap, metaBytes)) != GSA_SUCCESS ||
+            (s = ensure_bytes(ctx, &ctx->adbres, &ctx->adbres_cap, resBytes)) != GSA_SUCCESS ||
+            (s = ensure_bytes(ctx, &ctx->adbcodes, &ctx->adbcodes_cap, (size_t)maxCodes)) != GSA_SUCCESS)
+            return s;
+        if (passes > 1)
+        {
+            const size_t bb = (size_t)maxGrid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)(cmax + 1) * sizeof(int2);
+            if ((s = ensure_bytes(ctx, &ctx->dbbnd, &ctx->dbbnd_cap, bb)) != GSA_SUCCESS) return s;
+        }
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        char* const meta = (char*)ctx->adbmeta;
+        std::vector<char> hmeta(lenAt + maxN * 4), hres(resBytes);
+        for (const auto& ch : chunks)
+        {
+            const size_t n = ch.second - ch.first;
+            const int ntasks = (int)((n + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+            const int grid = std::max(1, std::min(wgs, (ntasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+            std::memset(hmeta.data(), 0, 64);
+            long long* const hoff = (long long*)(hmeta.data() + offAt);
+            long long* const hcoff = (long long*)(hmeta.data() + coffAt);
+            long long* const hmoff = (long long*)(hmeta.data() + moffAt);
+            int* const hlen = (int*)(hmeta.data() + lenAt);
+            int64_t cb = 0, mb = 0;
+            for (size_t k = 0; k < n; ++k)
+            {
+                const int h = lanes[ch.first + k];
+                hoff[k] = (long long)db_off[hits[h]];
+                hlen[k] = (int)len_of(h);
+                hcoff[k] = cb;
+                hmoff[k] = mb;
+                cb += gsa::dbtrace_code_bytes(R, hlen[k]);
+                mb += R + hlen[k];
+            }
+            gsa::DbTraceArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.fill.query = query;
+            a.fill.db = db;
+            a.fill.subst = subst;
+            a.fill.substsz = substsz;
+            a.fill.go = gapo;
+            a.fill.ge = gape;
+            a.fill.R = (int)R;
+            a.fill.passes = passes;
+            a.fill.nsubj = (int)n;
+            a.fill.ntasks = ntasks;
+            a.fill.off = (const long long*)(meta + offAt);
+            a.fill.len = (const int*)(meta + lenAt);
+            a.fill.out = (gsa::DbLanesOut*)(meta + foutAt);
+            a.fill.counter = (unsigned*)meta;
+            a.fill.bnd = passes > 1 ? (int2*)ctx->dbbnd : nullptr;
+            a.fill.bndStride = cmax + 1;
+            a.codes = (unsigned char*)ctx->adbcodes;
+            a.codeOff = (const long long*)(meta + coffAt);
+            a.moveOff = (const long long*)(meta + moffAt);
+            a.res = (gsa::DbTraceOut*)ctx->adbres;
+            a.moves = (unsigned char*)ctx->adbres + movAt;
+            a.local = local;
+            if ((e = hipMemcpyAsync(meta, hmeta.data(), hmeta.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            if ((e = gsa::launch_dbtrace(a, grid, ctx->adbev, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            note_launch(ctx);
+            if ((e = hipMemcpyAsync(hres.data(), ctx->adbres, movAt + (size_t)mb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            float m0 = 0.f, m1 = 0.f;
+            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+            fill_ms += m0;
+            walk_ms += m1;
+            const gsa::DbTraceOut* const ho = (const gsa::DbTraceOut*)hres.data();
+            for (size_t k = 0; k < n; ++k)
+            {
+                const int h = lanes[ch.first + k];
+                gsa_align_db_result& r = out[h];
+                r.score = ho[k].score;
+                r.i_start = ho[k].i_start;
+                r.j_start = ho[k].j_start;
+                r.i_end = ho[k].i_end;
+                r.j_end = ho[k].j_end;
+                if (ho[k].moves < 0 || ho[k].moves > R + hlen[k]) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                cig[(size_t)h] = fold_cigar((const unsigned char*)hres.data() + movAt + hmoff[k], ho[k].moves);
+            }
+            inf.chunks += 1;
+            inf.tasks += ntasks;
+            inf.code_bytes = std::max<int64_t>(inf.code_bytes, cb);
+        }
+        inf.lane_hits = (int32_t)lanes.size();
+    }
+    if (!other.empty())
+    {
+        // score and end cell from the score path; its launch record is not this call's to leave
+        const gsa_launch_info ll = ctx->ll;
+        const hipStream_t lls = ctx->ll_stream;
+        const unsigned e0 = ctx->ll_epoch0, e1 = ctx->ll_epoch;
+        std::vector<gsa_pair_dev> pairs(other.size());
+        std::vector<gsa_score_result> res(other.size());
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            gsa_pair_dev& p = pairs[k];
+            std::memset(&p, 0, sizeof(p));
+            p.seqY = query;
+            p.adjrows = adjq;
+            p.seqX = db + db_off[hits[other[k]]];
+            p.adjcols = (int32_t)(len_of(other[k]) + 1);
+        }
+        const int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local,
+                                       res.data(), &other_ms, st);
+        ctx->ll = ll;
+        ctx->ll_stream = lls;
+        ctx->ll_epoch0 = e0;
+        ctx->ll_epoch = e1;
+        if (s != GSA_SUCCESS) return s;
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            gsa_align_db_result& r = out[other[k]];
+            r.score = res[k].score;
+            r.i_end = res[k].i_end;
+            r.j_end = res[k].j_end;
+            r.status = 1;
+        }
+        inf.unsupported = (int32_t)other.size();
+    }
+    // the strings back to back in hit order; a hit's offset does not depend on the buffer's size
+    int64_t at = 0;
+    for (int h = 0; h < nhits; ++h)
+    {
+        gsa_align_db_result& r = out[h];
+        const int64_t len = (int64_t)cig[(size_t)h].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)h].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+    }
+    if (cigar_need) *cigar_need = at;
+    inf.fill_ms = fill_ms;
+    inf.walk_ms = walk_ms;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = fill_ms + walk_ms + other_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                     int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
+                     char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info, float* kernel_ms,
+                     void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_db_impl(ctx, query, adjq, db, db_off, nsubj, hits, nhits, subst, substsz, gapo, gape, local,
+                         scratch_limit, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
 
 int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                         int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_kernel_ms,

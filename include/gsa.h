@@ -409,6 +409,65 @@ int gsa_score_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int
                      const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz,
                      int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
                      float* kernel_ms, void* stream);
+
+/* Alignments of chosen subjects of a database search. */
+typedef struct gsa_align_db_result {
+    int32_t score;
+    int32_t status;              /* 0 aligned; 1 outside the trace kernel's limits: score and end cell only,
+                                    empty CIGAR; 2 CIGAR did not fit cigar_cap */
+    int64_t i_start, j_start, i_end, j_end;
+    int64_t cigar_off, cigar_len; /* into `cigar`; NUL-terminated there, the NUL not counted */
+} gsa_align_db_result;
+
+typedef struct gsa_align_db_info {  /* what the call ran; optional out-parameter */
+    int32_t lane_hits;      /* hits traced on the device */
+    int32_t unsupported;    /* hits with status 1 */
+    int32_t chunks;         /* fill + walk launch pairs */
+    int64_t tasks;          /* wave tasks over all chunks */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    float fill_ms, walk_ms; /* hipEvent time of the fill and of the walk launches, summed over the chunks */
+} gsa_align_db_info;
+
+/* The alignments of nhits subjects of a database, traced on the device.  query, db, db_off, nsubj,
+ * subst, substsz, gapo, gape, local: exactly as gsa_score_db_dev takes them.  hits is a HOST array of
+ * nhits subject indices (0 ... nsubj - 1), in any order; a subject may be named twice.  out is a host
+ * array of nhits results, out[h] for hits[h].  Synchronous.
+ * Semantics: the recurrences and boundaries of gsa_score_dev; score, i_end and j_end are exactly what
+ * gsa_score_db_dev returns for that subject (local: the first maximal cell in row-major order).  The
+ * path is walked backwards from the end cell, starting in state H.  State H at cell i, j: local and
+ * H = 0: stop; else H = H[i-1][j-1] + s: diagonal; else H = F[i][j]: state F; else state E (row 0 of a
+ * global alignment is E only, column 0 F only).  State F: a vertical move to i-1, j; the gap was
+ * extended (stay in F) iff F[i-1][j] + gape > H[i-1][j] + gapo, strictly, else opened (back to H).
+ * State E: the same along the row.  Global alignments stop at cell 0, 0.  i_start, j_start is the cell
+ * the path starts at: the aligned letters are query i_start+1 ... i_end and subject j_start+1 ... j_end.
+ * A local alignment of score 0 starts and ends at 0, 0 with an empty CIGAR.
+ * CIGAR: forward order, run-length encoded with decimal counts: '=' diagonal on equal letters, 'X'
+ * diagonal on different letters, 'I' vertical (a query letter only), 'D' horizontal (a subject letter
+ * only).  The strings go into `cigar` (cigar_cap bytes), NUL-terminated, back to back in hit order;
+ * a hit's offset does not depend on cigar_cap.  A string that does not fit is left out (status 2,
+ * the cells are still valid); *cigar_need (may be null) gets the bytes all strings need, so that a
+ * caller with a short buffer can call again; 2 (R + C) + 1 bytes per hit always suffice.
+ * Every traced hit keeps 4 bits per cell of move codes on the device until its path is walked:
+ * ceil(R / 384) x 384 x (C + 1) / 2 bytes.  scratch_limit is the bytes of codes the call may hold at
+ * once; 0 is the default, 256 MiB.  The hits are taken longest first and cut into chunks that fit;
+ * each chunk is one fill and one walk launch (nw_lanes_trace.hip) and one copy back.  The scratch is
+ * counted in the peaks of gsa_mem_stats.
+ * Status 1 -- score and end cell from gsa_score_batch_dev's path, no CIGAR: a hit whose codes alone
+ * exceed the limit, a subject of more than 8191 letters, a query whose profile does not fit LDS, a
+ * local pair whose score bound reaches 2^18, a pair whose value bound (largest |table value| x the
+ * shorter length + |gapo| + (R + C) |gape|) reaches 2^26.  No score depends on the route.  A subject with no
+ * letters is answered on the host (global: R x 'I'; local: score 0, empty CIGAR), as is an empty query.
+ * Everything gsa_score_db_dev rejects, a null hits with nhits > 0, a hit outside 0 ... nsubj - 1, a
+ * negative nhits, scratch_limit or cigar_cap, a null out, a null cigar with cigar_cap > 0 or a null
+ * context is errorInvalidValue before anything is enqueued; nhits = 0 succeeds with nothing launched.
+ * *info (may be null) says what the call ran.  This call adds no launch kind and no knob: the record
+ * of gsa_last_launch is left untouched, also by the status 1 hits' score launches.  *kernel_ms (may be
+ * null) gets the hipEvent time of all kernels of the call. */
+int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                     int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
+                     char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info,
+                     float* kernel_ms, void* stream);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
