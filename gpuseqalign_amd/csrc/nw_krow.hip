@@ -217,6 +217,13 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
     }
     const uint32_t ring_in = L.ring + (uint32_t)w * (kRing * 4u);
     const uint32_t ring_out = L.ring + (uint32_t)(w + 1) * (kRing * 4u);
+    // The block's two ring addresses in ONE VGPR: lane 0 holds its halo address (ring_in element
+    // 16b + 64), the other lanes the hand-off address (ring_out element 16b; lane 63 writes).  It
+    // advances by a block (64 bytes, modulo the ring) after each hand-off: 3 VALU per block where the
+    // two addresses rebuilt from b cost 8 instructions (5 SALU and a v_mov each way), and the
+    // wave's time is what it issues (100k 5.07 -> 4.99 ms, profiles/r07_block_start_ab.txt)
+    const uint32_t rbase = lane == 0 ? ring_in : ring_out;
+    uint32_t roff = lane == 0 ? 4u * 64u : 0u;  // block 0's
     const uint32_t f_in = L.flags + kr_prog(w), f_out = L.flags + kr_prog(w + 1);  // f_out: {prog[w+1], cons[w]}
     const uint32_t c_out = L.flags + kr_cons(w + 1);
     const uint32_t f_xo = L.flags + kFXo;
@@ -229,6 +236,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
 
     // block b needs its halo (ring elements 16b+64 .. 16b+79), room in ring_out for elements
     // 16b .. 16b+15, and (strip 0; the others trail it) the profile of block b+1 (columns < 16b+32)
+    // (spin()'s test; block() makes the same test on the words it read in mid-block, folded into one)
     auto ok = [&](int pin, int pco, int pxo, int b) {
         return pin >= kBlk * b + 64 + kBlk && pco >= kBlk * b + kBlk - kRing && (w != 0 || pxo >= kBlk * b + 2 * kBlk);
     };
@@ -285,7 +293,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
             // lane 0 alone (exec set and restored inside the asm: no divergent branch in the
             // block); the other lanes' registers keep their 0; the reads are awaited here (the
             // compiler cannot count them), as the first step needs them anyway
-            const uint32_t hb = ring_in + 4u * (uint32_t)((kBlk * b + 64) & (kRing - 1));
+            const uint32_t hb = rbase + roff;  // (lane 0: ring_in element 16b + 64; b is the block under way)
             uint64_t sv;
             asm volatile(
                 "s_mov_b64 %4, exec\n"
@@ -349,7 +357,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
     auto handoff = [&](int bb) {
         {
             // lane 63 alone (exec set and restored inside the asm)
-            const uint32_t eb = ring_out + 4u * (uint32_t)((kBlk * bb) & (kRing - 1));
+            const uint32_t eb = rbase + roff;  // (lane 63: ring_out element 16bb; bb is the block under way)
             uint64_t sv;
             asm volatile(
                 "s_mov_b64 %0, exec\n"
@@ -407,7 +415,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
     auto halo_stage = [&](int b) {
         if constexpr (PT == 3)
         {
-            const uint32_t hb = ring_in + 4u * (uint32_t)((kBlk * b + 64) & (kRing - 1));
+            const uint32_t hb = rbase + roff;  // (lane 0: ring_in element 16b + 64; b is the block under way)
             const uint32_t sa = xsData + 64u * (uint32_t)(4 * ((b - 1) % kXD));
             uint64_t sv;
             asm volatile(
@@ -438,6 +446,10 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
     };
     int rpin = 0, rpco = 0, rpxo = 0;  // progress words read in mid-block, checked at the next block
     int rsink = 0;                     // the read's 4th dword (unused)
+    // what block()'s folded test adds to rpxo: xo's threshold lies 48 below prog's (16 b + 32 against
+    // 16 b + 80); strips other than 0 do not wait for xo, and their slot's second word (cons[w-1],
+    // 0 .. kBig) + kBig passes every threshold without overflowing
+    const int xoAdd = (w == 0) ? 64 + kBlk - 2 * kBlk : kBig;
     // Tile boundaries bc = jb*tBx are multiples of 16 columns, and lane l meets column bc at step
     // bc + l: in block bc/16 + l/16, at step l & 15.  So the 4 blocks from bc/16 on capture it, 16
     // lanes each, and every lane picks the block's step (lane & 15): the selection masks are
@@ -461,14 +473,25 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
         if (ldgEnd) ldg[3] += lt0 - ldgEnd;
 #endif
         {
-            const int pin = __builtin_amdgcn_readfirstlane(rpin), pco = __builtin_amdgcn_readfirstlane(rpco);
-            const int pxo = (w == 0) ? __builtin_amdgcn_readfirstlane(rpxo) : 0;
+            // ok() of the words read in mid-block, folded into one test: each word plus the distance
+            // of its threshold below ok()'s first (16 b + 80), the smallest of the three sums (2 adds
+            // and a v_min3 on the read's own registers) through ONE v_readfirstlane against 16 b + 80.
+            // A lone wave issues an instruction every ~4.5 cycles whatever its kind, so the block's
+            // start costs what it issues: the three v_readfirstlane, the three thresholds rebuilt
+            // from b and their compares, selects and ands were ~23 instructions, these are ~8
+            // (100k 5.30 -> 5.06 ms, profiles/r07_block_start_ab.txt).
+            // The wait the compiler puts before the first use of the read's registers is
+            // lgkmcnt(1): it counts the read and the progress write behind it but not the hand-off's
+            // asm writes between them, so it covers those too (the queue executes in order).  That
+            // costs nothing that the halo's lgkmcnt(0) below would not: with the halo read ahead of
+            // this test and one wait for both, the fill is slower (same file).
+            const int slack = __builtin_amdgcn_readfirstlane(min(min(rpin, rpco + (64 + kRing)), rpxo + xoAdd));
             // every destination register of the progress read stays allocated until here: a dead
             // one reused by the block's last steps is a write-after-write on an LDS load, which
             // the compiler resolves with lgkmcnt(1) there -- a wait for the whole LDS queue (the
             // profile reads and the hand-off writes) on the critical path of every block
             asm volatile("" ::"v"(rpin), "v"(rpco), "v"(rpxo), "v"(rsink));
-            if (!ok(pin, pco, pxo, b) && !spin(b)) return false;
+            if (slack < kBlk * b + 64 + kBlk && !spin(b)) return false;
         }
         if (PT == 3 && b > 0)
             halo_stage(b);
@@ -529,6 +552,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
         const uint64_t lt2 = GSA_LDG_T();
 #endif
         handoff(b);
+        roff = (roff + 4u * kBlk) & (4u * kRing - 1);  // the next block's ring addresses
         if constexpr (PT == 4 && !RAMP)
             if ((b & 15) == 15)
             {
