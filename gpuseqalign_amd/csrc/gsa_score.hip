@@ -1,0 +1,1323 @@
+// gsa_score.hip -- the score-only and database entry points of libgsa.so (declared in include/gsa.h):
+// gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev and gsa_align_db_dev, on the K-rows
+// and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan (nw_scan.hip), NW / SW from both
+// ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip, nw_lanes_trace.hip).  The context
+// and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/gsa.h"
+#include "gsa_ctx.h"
+#include "nw_bidi.h"
+#include "nw_krow.h"
+#include "nw_lanes.h"
+#include "nw_lanes_trace.h"
+#include "nw_scan.h"
+#include "nw_strip.h"
+
+namespace {
+
+// Score-only kernels: global alignments run on the strip kernel in its affine mode (shifted
+// Gotoh, nw_strip.hip kModeScoreAG); local ones on the row scan (nw_scan.hip).  GSA_SCORE_SCAN=1
+// sends global ones to the row scan as well (tests compare the two).
+bool score_scan_forced(const gsa_ctx* ctx)
+{
+    const char* e = knob(ctx, "GSA_SCORE_SCAN");
+    return e && std::atoi(e) == 1;
+}
+
+constexpr int kScoreTooLarge = 1000;  // internal: score_ag_strip -> row scan
+
+// score-only fills on the K-rows layout (default) or, with GSA_SCORE_KERNEL=strip, the strip kernel
+bool score_kernel_krow(const gsa_ctx* ctx)
+{
+    const char* e = knob(ctx, "GSA_SCORE_KERNEL");
+    return !(e && std::strcmp(e, "strip") == 0);
+}
+
+// SW end-cell keys: score << bits | (2^bits-1 - row-major index), bits = ceil(log2((R+1)(C+1)));
+// scores (< 2^31) keep 63 - bits >= 29 bits up to (R+1)(C+1) = 2^34
+int sw_idx_bits(int64_t R, int64_t C) { return gsa::sw_idx_bits(R, C); }
+
+// Score-only NW from both ends (nw_bidi.h): a single pair's wavefront time is (C + strips x hop)
+// steps, and at 50k the strips' fill-in is ~30 % of it; the top half (rows 1..m) forward and the
+// bottom half reversed (rows R..m+1 of the reversed pair) run at the same time, each with half the
+// strips, as two pairs of one launch with their tickets interleaved, and a combine kernel takes the
+// best crossing of the rows where they meet.  m = K floor(R/2K), so that row m of the top and row
+// R - m of the reversed bottom are both a lane's last row (the strips' tap); R % K != 0 takes the
+// one-direction path.
+// Local modes (SW) run three pairs: the top half forward, the bottom half reversed, and the bottom
+// half forward from a fresh (zero) border, whose end-cell keys (offset by m rows) share the top's
+// swBest.  The keys then hold the best cell of every alignment that does not cross row m, first in
+// row-major order, and the combine the best score through row m (M_cross).  If M_cross is below
+// that score, or equal to it with the key's cell in the top half (before every crossing end), the
+// key is the answer; otherwise an alignment through row m may end earlier or score more: when the top
+// half ended on a ticket boundary, a second launch continues the pair from its ticket there, its row
+// above the top's last-ticket granules (restamped), and the answer is the better of the top's keys
+// and that run's (GSA_BIDI_SW_CONT=0: not); else the caller runs the one-direction kernel
+// (kBidiFallback).
+constexpr int kScoreTooLargeB = -1001;
+constexpr int kBidiFallback = -1002;
+int score_bidi(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX, int64_t C, const int32_t* subst,
+               int32_t substsz, int32_t gapo, int32_t gape, int K, bool transposed, gsa_score_result* out,
+               hipStream_t st, bool local = false)
+{
+    const int64_t TR = (int64_t)(64 * K) * gsa::kSparseNS;
+    const bool affine = gapo != gape;
+    // The split.  A half whose rows end on a ticket boundary needs no lane tap: its last ticket's
+    // drain writes that row to the granules like any other ticket's, and the combine reads it there.
+    // A lane tap costs its strip 8 global stores per block, and as the half's last strip it sets the
+    // half's end (50k NW-AG 2.94 ms with no tap, 3.19 with two lane taps).  So the top half ends on a
+    // ticket boundary and takes the rows that make both halves end together: skew = p C 64K / (2 hop)
+    // rows past R/2, p the lane tap's share of the C steps (0.117 affine, 0.05 linear: 8 / 4 stores
+    // per block) and hop ~96 steps between strips; the bottom, when R is a multiple of the ticket too,
+    // is free as well and the split even.  Short pairs keep two lane taps (m = K floor(R/2K)).
+    int64_t m = (int64_t)K * (R / (2 * K));
+    bool topFree = false, botFree = false;
+    if (R >= 4 * TR && env_int(ctx, "GSA_BIDI_GRAN", 1))
+    {
+        const int skewEnv = env_int(ctx, "GSA_BIDI_SKEW", -1);
+        // (local linear: 0.075, the third pair's share of the chip moves the balance; 50k SW-LG
+        // 2.78 -> 2.76 ms, profiles/r05_sw_skew.txt)
+        const double p = affine ? 0.117 : local ? 0.075 : 0.05;
+        const bool both = R % TR == 0;
+        const int64_t skew = both ? 0 : skewEnv >= 0 ? skewEnv : (int64_t)(p * (double)C * 64.0 * K / (2.0 * 96.0));
+        int64_t mt = TR * (int64_t)llround((double)(R / 2 + skew) / (double)TR);
+        mt = std::min(std::max(mt, TR), (R - 2 * K) / TR * TR);
+        if (mt >= TR && R - mt >= 2 * K && (R - mt) % K == 0)
+        {
+            m = mt;
+            topFree = true;
+            botFree = both;
+        }
+    }
+    const int64_t mb = R - m;
+    const int64_t tkTop = (m + TR - 1) / TR, tkBot = (mb + TR - 1) / TR;
+    const int nP = local ? 3 : 2;
+    const size_t tapLen = ((size_t)gsa::kTapPad + (size_t)C + 160 + 63) & ~(size_t)63;
+    // layout (ints): tap rows H, F of the top, then of the bottom; reversed Y (mb + 1), reversed X
+    // (C + 1), the combine's result
+    const size_t oRY = 4 * tapLen, oRX = oRY + (size_t)mb + 1, oRes = (oRX + (size_t)C + 1 + 63) & ~(size_t)63;
+    const size_t oSub = oRes + 64;  // transposed: the table transposed
+    const size_t need = oSub + (size_t)substsz * (size_t)substsz;
+    hipError_t e;
+    int s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], need * sizeof(int))) != GSA_SUCCESS ||
+        (s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS)
+        return s;
+    int* const bidi = ctx->buf[kBufBidi].as<int>();
+    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+    int* tapH = bidi;
+    int* tapF = tapH + tapLen;  // half 1: + 2 tapLen
+    int* ry = bidi + oRY;
+    int* rx = bidi + oRX;
+    int* res = bidi + oRes;
+    int* substT = transposed ? bidi + oSub : nullptr;
+    if ((s = ensure_desc(ctx, local ? 4 : 2)) != GSA_SUCCESS) return s;
+    const size_t stride = (size_t)gsa::gran_stride((int)C);
+    const size_t granAll = (size_t)(tkTop + (nP - 1) * tkBot) * stride;
+    const int64_t tkAll = (R + TR - 1) / TR;  // local, the way back: the whole pair's tickets
+    if ((s = ensure_gran(ctx, 2 * granAll + (local ? 2 * (size_t)tkAll * stride : 0), st)) != GSA_SUCCESS) return s;
+    gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
+    unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+    gsa::PairDesc d[3];
+    std::memset(d, 0, sizeof(d));
+    d[0].seqY = seqY;
+    d[0].seqX = seqX;
+    d[0].R = (int)m;
+    d[0].nTickets = (int)tkTop;
+    d[0].granOff = 0;
+    d[1].seqY = ry;
+    d[1].seqX = rx;
+    d[1].R = (int)mb;
+    d[1].nTickets = (int)tkBot;
+    d[1].granOff = (long long)((size_t)tkTop * stride);
+    // local: the bottom half forward, rows m+1 .. R (seqY + m: its element 0 is row m's letter,
+    // unused), from a fresh border
+    d[2].seqY = seqY + m;
+    d[2].seqX = seqX;
+    d[2].R = (int)mb;
+    d[2].nTickets = (int)tkBot;
+    d[2].granOff = (long long)((size_t)(tkTop + tkBot) * stride);
+    d[2].rowOff = (int)m;
+    // local: keys of the top (StripArgs::swBest, word 1), of the reversed bottom (word 4, unused) and
+    // of the fresh bottom (word 5)
+    if (local)
+    {
+        d[1].swBest = sctl + 4;
+        d[2].swBest = sctl + 5;
+    }
+    for (int h = 0; h < 3; ++h) d[h].C = d[h].Cp = (int)C;
+    const int mode = local ? (affine ? gsa::kModeScoreSW : gsa::kModeScoreSWL) : affine ? gsa::kModeScoreAG : gsa::kModeScoreAGL;
+    const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+    const int q8 =
+        (q8env != 0 && (q8env == 2 || K == 4) && gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+    gsa::StripArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.subst = transposed ? substT : subst;
+    a.substsz = substsz;
+    a.g = gapo;
+    a.go = gapo;
+    a.ge = gape;
+    a.ns = gsa::kSparseNS;
+    a.pairs = ddesc;
+    a.nPairs = nP;
+    a.nTicketsTotal = (int)(tkTop + (nP - 1) * tkBot);
+    a.bidiTop = (int)tkTop;
+    a.bidiMid = local ? (int)tkBot : 0;
+    a.gran = dgran;
+    a.gran2 = dgran + granAll;
+    a.ticket = ctx->ctl;
+    a.q8flag = ctx->ctl + 2;
+    a.err = (unsigned*)(sctl + 3);
+    a.agResult = (int*)sctl;
+    a.swBest = sctl + 1;
+    a.spin = ctx->spin_ticks;
+    a.idxBits = sw_idx_bits(R, C);
+    a.epoch = ++ctx->epoch;
+    if (a.epoch == 0) a.epoch = ++ctx->epoch;
+    a.q8 = q8;
+    a.tapRow = topFree ? 0 : (int)m;
+    a.tapRowB = botFree ? 0 : (int)mb;
+    a.tapGran = (topFree ? 1 : 0) | (botFree ? 2 : 0);
+    a.tapH = tapH;
+    a.tapF = tapF;
+    a.tapStride = (int)(2 * tapLen);
+    (void)hipEventRecord(ctx->ev0, st);
+    if ((e = gsa::launch_bidi_prep(d[0], d[1], ddesc, seqY, (int)m, (int)R, seqX, (int)C, ry, rx, ctx->ctl, sctl,
+                                   res, subst, substsz, substT, st, local ? &d[2] : nullptr)) != hipSuccess ||
+        (e = gsa::launch_krow_score(a, mode, K, std::max(1, std::min(a.nTicketsTotal, ctx->cu_count)), st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    note_launch(ctx);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, a.epoch);
+        li.ns = a.ns;
+        li.k = K;
+        li.q8 = q8;
+        li.both_ends = 1;
+        li.npairs = nP;
+        li.tickets = a.nTicketsTotal;
+    }
+    // the rows where the halves meet: a lane tap (tap rows, one int per column from kTapPad), or the
+    // half's last-ticket granules (the low word of each 64-bit granule)
+    const int* gTop = (const int*)(dgran + (size_t)(tkTop - 1) * stride);
+    const int* gBot = (const int*)(dgran + (size_t)(tkTop + tkBot - 1) * stride);
+    const int* tH = topFree ? gTop : tapH + gsa::kTapPad;
+    const int* tF = topFree ? gTop + 2 * granAll : tapF + gsa::kTapPad;
+    const int* bH = botFree ? gBot : tapH + 2 * tapLen + gsa::kTapPad;
+    const int* bF = botFree ? gBot + 2 * granAll : tapF + 2 * tapLen + gsa::kTapPad;
+    if ((e = gsa::launch_bidi_combine(tH, tF, topFree ? 2 : 1, bH, bF, botFree ? 2 : 1, (int)m, (int)mb, (int)C, gapo,
+                                      gape, affine, res, st, local)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    (void)hipEventRecord(ctx->ev1, st);
+    unsigned long long rw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int score = 0;
+    if ((e = hipMemcpyAsync(rw, sctl, sizeof(rw), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(&score, res, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
+    const unsigned err = (unsigned)rw[3];
+    if (err == 2u) return kScoreTooLargeB;  // a value outside int16: the row scan
+    if (err != 0) return GSA_ERROR_KERNEL_FAILURE;
+    if (local)
+    {
+        if (rw[0] & 1u) return kScoreTooLargeB;  // a score >= 2^26: the row scan
+        const int bits = sw_idx_bits(R, C);
+        const unsigned long long mask = (1ull << bits) - 1;
+        unsigned long long key = std::max(rw[1], rw[5]);  // top, fresh bottom
+        unsigned long long idx = key ? mask - (key & mask) : 0;
+        long long best = key ? (long long)(key >> bits) : 0;
+        const long long ie = (long long)(idx / (unsigned long long)(C + 1));
+        const bool fallback = !((long long)score < best || ((long long)score == best && ie <= m));
+        const bool cont = fallback && topFree && env_int(ctx, "GSA_BIDI_SW_CONT", 1) != 0;
+        if (env_int(ctx, "GSA_BIDI_LOG", 0))  // (tests: which way the pair went)
+            std::fprintf(stderr, "gsa local both ends: m %lld, through m %d, best off it %lld at row %lld -> %s\n",
+                         (long long)m, score, best, ie,
+                         !fallback ? "answer" : cont ? "bottom again from row m" : "one direction");
+        if (fallback && !cont) return kBidiFallback;
+        if (cont)
+        {
+            // the pair from ticket tkTop on, its row above the top's last-ticket granules, in a granule
+            // area of its own (its later tickets must not meet another half's granules)
+            unsigned long long* seedH = dgran + 2 * granAll;
+            unsigned long long* seedF = seedH + (size_t)tkAll * stride;
+            unsigned ep2 = ++ctx->epoch;
+            if (ep2 == 0) ep2 = ++ctx->epoch;
+            const size_t last = (size_t)(tkTop - 1) * stride;
+            gsa::PairDesc dc;
+            std::memset(&dc, 0, sizeof(dc));
+            dc.seqY = seqY;
+            dc.seqX = seqX;
+            dc.R = (int)R;
+            dc.C = dc.Cp = (int)C;
+            dc.nTickets = (int)tkAll;
+            dc.swBest = sctl + 6;
+            gsa::StripArgs b = a;
+            b.pairs = ddesc + 3;
+            b.nPairs = 1;
+            b.bidiTop = b.bidiMid = 0;
+            b.nTicketsTotal = (int)(tkAll - tkTop);
+            b.tkFirst = (int)tkTop;
+            b.gran = seedH;
+            b.gran2 = seedF;
+            b.epoch = ep2;
+            b.tapRow = b.tapRowB = b.tapGran = 0;
+            if ((e = hipMemcpyAsync(ddesc + 3, &dc, sizeof(dc), hipMemcpyHostToDevice, st)) != hipSuccess ||
+                (e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess ||
+                (e = hipMemsetAsync(sctl, 0, 8, st)) != hipSuccess ||
+                (e = hipMemsetAsync(sctl + 6, 0, 8, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            if ((e = gsa::launch_bidi_seed(dgran + last, affine ? dgran + granAll + last : nullptr, seedH + last,
+                                           affine ? seedF + last : nullptr, (long long)stride, ep2, st)) != hipSuccess ||
+                (e = gsa::launch_krow_score(b, mode, K, std::max(1, std::min(b.nTicketsTotal, ctx->cu_count)), st)) !=
+                    hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            note_launch(ctx);
+            ctx->ll_epoch = ep2;  // (the record stays the both-ends call's; the word is this launch's)
+            (void)hipEventRecord(ctx->ev1, st);
+            if ((e = hipMemcpyAsync(rw, sctl, sizeof(rw), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
+            const unsigned err2 = (unsigned)rw[3];
+            if (err2 == 2u) return kScoreTooLargeB;
+            if (err2 != 0) return GSA_ERROR_KERNEL_FAILURE;
+            if (rw[0] & 1u) return kScoreTooLargeB;
+            key = std::max(rw[1], rw[6]);  // the top's keys (word 1 is not touched again), the rest's
+            idx = key ? mask - (key & mask) : 0;
+            best = key ? (long long)(key >> bits) : 0;
+        }
+        out->score = (int32_t)best;
+        out->i_end = (int64_t)(idx / (unsigned long long)(C + 1));
+        out->j_end = (int64_t)(idx % (unsigned long long)(C + 1));
+        return GSA_SUCCESS;
+    }
+    out->score = score;
+    out->i_end = transposed ? C : R;
+    out->j_end = transposed ? R : C;
+    return GSA_SUCCESS;
+}
+
+int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX, int64_t C, const int32_t* subst,
+                   int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, hipStream_t st)
+{
+    // the K-rows score kernel's rows per lane, tickets of 64 K NS rows: 2 in the modes with the
+    // longer step (SW tracking, affine gaps: the block's fixed part is a smaller share there, and
+    // twice the strips shorten it), 4 for NW-LG; same box, 5k-100k pairs: NW-AG -5..-7 %, SW-AG
+    // -9..-11 %, SW-LG -2..-5 % with 2, NW-LG +12..18 % (profiles/r04_score_k.txt).  GSA_SCORE_K
+    // = 2 / 4 forces one
+    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
+    const int scoreK = kenv == 2 || kenv == 4 ? kenv : (!local && gapo == gape) ? 4 : 2;
+    // the K-rows score kernel unless GSA_SCORE_KERNEL=strip, or its LDS (a profile of substsz rows)
+    // does not fit, or SW with ge > 0 (its per-row key offsets assume z grows along j); the strip
+    // kernel's score modes otherwise, on its own 1024-row tickets
+    const bool krow = score_kernel_krow(ctx) && (!local || gape <= 0) && gsa::krow_score_lds_bytes(substsz) <= ctx->lds_max;
+    const int64_t TR = krow ? (int64_t)(64 * scoreK) * gsa::kSparseNS : (int64_t)gsa::kWaveRows * gsa::kSparseNS;
+    const int64_t tickets = (R + TR - 1) / TR;
+    if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+    // NW from both ends (score_bidi) when each half keeps >= 4 tickets, at 2 rows per lane in both
+    // NW modes (its halves have half the strips, so the shorter block wins for NW-LG too: 50k 2.25 ->
+    // 2.11 ms, profiles/r05_bidi_ab.txt).  GSA_SCORE_BIDI: 0 never, 2 at any size (tests)
+    // A pair whose R is not a multiple of K but whose C is runs transposed (X down the rows, Y along
+    // them, the table transposed: the same global score, and gaps cost the same either way).
+    const int bidi = env_int(ctx, "GSA_SCORE_BIDI", 1);
+    const int kb = kenv == 2 || kenv == 4 ? kenv : 2;
+    const int64_t TRb = (int64_t)(64 * kb) * gsa::kSparseNS;
+    auto splits = [&](int64_t rows) { return rows % kb == 0 && rows >= 2 * kb && (bidi == 2 || rows >= 8 * TRb); };
+    if (krow && !local && bidi != 0 && (splits(R) || splits(C)))
+    {
+        const bool tr = !splits(R);
+        const int sb = tr ? score_bidi(ctx, seqX, C, seqY, R, subst, substsz, gapo, gape, kb, true, out, st)
+                          : score_bidi(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, kb, false, out, st);
+        return sb == kScoreTooLargeB ? kScoreTooLarge : sb;
+    }
+    // local: from both ends only by rows (the end cell's row-major tie rule does not survive a
+    // transpose), and back to one direction when an alignment through the split may decide it
+    float bidiMs = 0.f;
+    if (krow && local && bidi != 0 && env_int(ctx, "GSA_SCORE_BIDI_SW", 1) && splits(R))
+    {
+        const int sb = score_bidi(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, kb, false, out, st, true);
+        if (sb == kScoreTooLargeB) return kScoreTooLarge;
+        if (sb != kBidiFallback) return sb;
+        bidiMs = out->calc_kernel_ms;
+    }
+    gsa::StripArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.subst = subst;
+    a.substsz = substsz;
+    a.g = gapo;
+    a.go = gapo;
+    a.ge = gape;
+    a.ns = gsa::kSparseNS;
+    gsa::PairDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.seqY = seqY;
+    d.seqX = seqX;
+    d.R = (int)R;
+    d.C = (int)C;
+    d.Cp = (int)C;
+    d.nTickets = (int)tickets;
+    int s = ensure_desc(ctx, 1);
+    if (s != GSA_SUCCESS) return s;
+    gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
+    hipError_t e = hipMemcpyAsync(ddesc, &d, sizeof(d), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    const size_t gran = (size_t)tickets * (size_t)gsa::gran_stride((int)C);
+    if ((s = ensure_gran(ctx, 2 * gran, st)) != GSA_SUCCESS) return s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
+    unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+    a.pairs = ddesc;
+    a.nPairs = 1;
+    a.nTicketsTotal = (int)tickets;
+    a.gran = dgran;
+    a.gran2 = dgran + gran;
+    a.ticket = ctx->ctl;
+    // an error word of its own: a fill enqueued earlier on this stream keeps its sticky error for
+    // the caller's gsa_sync, and its error does not read as this launch's
+    a.err = (unsigned*)(sctl + 3);
+    a.spin = ctx->spin_ticks;
+    a.agResult = (int*)sctl;
+    a.swBest = sctl + 1;
+    a.idxBits = sw_idx_bits(R, C);
+    a.epoch = ++ctx->epoch;
+    if (a.epoch == 0) a.epoch = ++ctx->epoch;
+    if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    (void)hipEventRecord(ctx->ev0, st);
+    const int grid = std::max(1, std::min((int)tickets, ctx->cu_count));
+    // a linear gap (gapo == gape) runs the step without E' and F' (d = 0)
+    const int mode = local ? (gapo == gape ? gsa::kModeScoreSWL : gsa::kModeScoreSW)
+                           : (gapo == gape ? gsa::kModeScoreAGL : gsa::kModeScoreAG);
+    // the int8 column profile where its LDS fits (the instance declines a table outside int8 and the
+    // int16 instance behind it runs) for the 4-rows-per-lane geometry (NW-LG): 50k 2.52 -> 2.46 ms;
+    // at 2 rows per lane the int16 profile is faster (SW-LG 3.71 -> 3.42 ms, NW-AG 4.16 -> 3.87;
+    // profiles/r04_score_k.txt).  GSA_KROW_Q8=0 / 2: int16 / int8 always
+    const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+    a.q8 = (q8env != 0 && (q8env == 2 || scoreK == 4) && gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+    a.q8flag = ctx->ctl + 2;
+    if ((e = krow ? gsa::launch_krow_score(a, mode, scoreK, grid, st) : gsa::launch_strip_fill(a, mode, grid, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    note_launch(ctx);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, krow ? GSA_LAUNCH_SCORE_KROW : GSA_LAUNCH_SCORE_STRIP, st, a.epoch);
+        li.ns = a.ns;
+        li.k = krow ? scoreK : 1;
+        li.q8 = krow ? a.q8 : 0;
+        li.npairs = 1;
+        li.tickets = tickets;
+    }
+    (void)hipEventRecord(ctx->ev1, st);
+    unsigned long long res[4] = {0, 0, 0, 0};
+    if ((e = hipMemcpyAsync(res, sctl, sizeof(res), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    const unsigned err = (unsigned)res[3];
+    (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
+    out->calc_kernel_ms += bidiMs;  // (a local pair back from both ends: both launches)
+    // a substitution value outside int16 after the shift: the int32 row scan computes it
+    if (err == 2u) return kScoreTooLarge;
+    if (err != 0) return GSA_ERROR_KERNEL_FAILURE;
+    if (local)
+    {
+        if (res[0] & 1u) return kScoreTooLarge;  // a score >= 2^26: the caller takes the row scan
+        // max key: score << idxBits | (2^idxBits-1 - row-major index); 0 = no positive cell -> (0, 0, 0)
+        const int bits = sw_idx_bits(R, C);
+        const unsigned long long mask = (1ull << bits) - 1;
+        const unsigned long long idx = res[1] ? mask - (res[1] & mask) : 0;
+        out->score = (int32_t)(res[1] >> bits);
+        out->i_end = (int64_t)(idx / (unsigned long long)(C + 1));
+        out->j_end = (int64_t)(idx % (unsigned long long)(C + 1));
+        return GSA_SUCCESS;
+    }
+    out->score = (int32_t)(uint32_t)res[0];
+    out->i_end = R;
+    out->j_end = C;
+    return GSA_SUCCESS;
+}
+
+}  // namespace
+
+namespace {
+
+// Largest |substitution value| (>= 1) of a host table.
+long long subst_absmax(const int32_t* sub, int32_t substsz)
+{
+    long long smax = 1;
+    for (size_t k = 0; k < (size_t)substsz * (size_t)substsz; ++k)
+        smax = std::max<long long>(smax, sub[k] < 0 ? -(long long)sub[k] : (long long)sub[k]);
+    return smax;
+}
+
+// Value ranges of one pair (R, C >= 1), smax the largest |substitution value|, which bounds every
+// score and shifted value: errorInvalidValue when no kernel holds the pair; *stripOk: the strip /
+// K-rows score kernels do (else the row scan).
+int score_ranges(int64_t R, int64_t C, long long smax, int32_t gapo, int32_t gape, int32_t local, bool* stripOk)
+{
+    const long long span = (R + C) * (long long)(-gape) + (long long)(gape - gapo) + smax;
+    // unshifted int32 (row scan): |H| <= smax*min(R,C) + |go| + (R+C)|ge|
+    if (smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= (1ll << 30))
+        return GSA_ERROR_INVALID_VALUE;
+    const int bits = sw_idx_bits(R, C);
+    const long long scoreBound = std::min<long long>((1ll << 31) - 1, smax * std::min(R, C));
+    const int scoreBits = scoreBound > 0 ? 64 - __builtin_clzll((unsigned long long)scoreBound) : 1;
+    // SW end-cell keys (score << bits | ~index) must fit 64 bits: the row scan packs full scores
+    if (local && bits + scoreBits > 63) return GSA_ERROR_INVALID_VALUE;
+    // the strip kernel's SW mode needs go < 0 (cells past C then never tie the maximum) and scores
+    // below 2^26 packed with bits index bits (it reports larger ones); both modes keep shifted
+    // values (i+j)*ge apart within int32 with margin; otherwise the row scan
+    // (and scores below 2^26 by construction, so that no shifted key can wrap before the kernel flags it)
+    *stripOk = (!local || (gapo < 0 && bits + 27 <= 63 && smax * std::min(R, C) < (1ll << 26))) && span < (1ll << 28);
+    return GSA_SUCCESS;
+}
+
+// gsa_score_dev; smax < 0: read the table back from the device (in stream order, so the caller's
+// writes to it are seen) to find the largest |value|; gsa_score passes it from its host copy.
+int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                   gsa_score_result* out, hipStream_t st, long long smax)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0 (nw_scan.hip)
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    out->calc_kernel_ms = 0.f;
+    if (R == 0 || C == 0)
+    {
+        // one boundary: nothing to fill (score_oracle.c semantics)
+        const int64_t k = R + C;
+        out->score = (local || k == 0) ? 0 : (int32_t)(gapo + (k - 1) * gape);
+        out->i_end = local ? 0 : R;
+        out->j_end = local ? 0 : C;
+        return GSA_SUCCESS;
+    }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    // value ranges: the largest |substitution value| bounds every score and shifted value
+    if (smax < 0)
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+    }
+    bool stripOk = false;
+    if ((s = score_ranges(R, C, smax, gapo, gape, local, &stripOk)) != GSA_SUCCESS) return s;
+    if (!score_scan_forced(ctx) && stripOk)
+    {
+        s = score_ag_strip(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, local, out, st);
+        if (s != kScoreTooLarge) return s;
+    }
+    const int64_t nTR = (R + 63) / 64;
+    const size_t bnd = (size_t)(nTR + 1) * (size_t)(C + 1);
+    const size_t need = 2 * bnd + (size_t)(nTR + 1);  // bh, bf, prog
+    if ((s = reserve_hard(ctx, ctx->buf[kBufSbnd], need * sizeof(int))) != GSA_SUCCESS ||
+        (s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS)
+        return s;
+    int* const sbnd = ctx->buf[kBufSbnd].as<int>();
+    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+    gsa::ScoreArgs a {};
+    a.seqY = seqY;
+    a.seqX = seqX;
+    a.subst = subst;
+    a.substsz = substsz;
+    a.go = gapo;
+    a.ge = gape;
+    a.R = R;
+    a.C = C;
+    a.nTR = (int)nTR;
+    a.bh = sbnd;
+    a.bf = sbnd + bnd;
+    a.prog = sbnd + 2 * bnd;
+    a.ticket = (unsigned*)sctl;
+    a.err = (unsigned*)sctl + 1;
+    a.spin = ctx->spin_ticks;
+    a.best = sctl + 1;
+    a.idxBits = sw_idx_bits(R, C);
+    a.result = (int*)(sctl + 2);
+    if ((e = hipMemsetAsync(a.prog, 0, (size_t)(nTR + 1) * sizeof(int), st)) != hipSuccess ||
+        (e = hipMemsetAsync(sctl, 0, 64, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    (void)hipEventRecord(ctx->ev0, st);
+    if ((e = gsa::launch_score_scan(a, local, ctx->cu_count, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    {
+        gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_SCAN, st, 0);
+        li.k = 1;
+        li.npairs = 1;
+    }
+    (void)hipEventRecord(ctx->ev1, st);
+    unsigned long long ctl[3];
+    if ((e = hipMemcpyAsync(ctl, sctl, sizeof(ctl), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
+    if ((unsigned)(ctl[0] >> 32) != 0) return GSA_ERROR_KERNEL_FAILURE;  // a wait gave up
+    if (local)
+    {
+        const int bits = sw_idx_bits(R, C);
+        const unsigned long long mask = (1ull << bits) - 1;
+        const unsigned long long idx = mask - (ctl[1] & mask);
+        out->score = (int32_t)(ctl[1] >> bits);
+        out->i_end = (int64_t)(idx / (unsigned long long)(C + 1));
+        out->j_end = (int64_t)(idx % (unsigned long long)(C + 1));
+    }
+    else
+    {
+        out->score = (int32_t)(uint32_t)ctl[2];
+        out->i_end = R;
+        out->j_end = C;
+    }
+    return GSA_SUCCESS;
+}
+
+// gsa_score_batch_dev: the pairs the K-rows score kernel holds in one persistent launch (their
+// tickets in one ticket space, two result words per pair, decoded on the device), the others -- and
+// those the kernel flags -- one by one through score_dev_impl.
+int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_ms, hipStream_t st)
+{
+    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+    if (batch_ms) *batch_ms = 0.f;
+    // empty pairs: one boundary, nothing to fill (score_dev_impl)
+    std::vector<int> work;
+    for (int p = 0; p < npairs; ++p)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        out[p].calc_kernel_ms = 0.f;
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            out[p].score = (local || k == 0) ? 0 : (int32_t)(gapo + (k - 1) * gape);
+            out[p].i_end = local ? 0 : R;
+            out[p].j_end = local ? 0 : C;
+        }
+        else
+            work.push_back(p);
+    }
+    // the K-rows score kernel, under score_ag_strip's conditions for it (else every pair alone)
+    const bool krow = !score_scan_forced(ctx) && score_kernel_krow(ctx) && gsa::krow_score_lds_bytes(substsz) <= ctx->lds_max;
+    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
+    // rows per lane: 4 in every mode.  A single pair's rule (score_ag_strip: 2 for SW and affine gaps)
+    // shortens its critical path; a batch fills the chip either way, and the longer strip's smaller
+    // share of hand-off wins: 512 pairs of 18-22k, SW-LG 62.5 -> 47.6 ms, NW-AG 68.4 -> 49.7 ms,
+    // NW-LG 54.1 -> 29.3 ms (profiles/score_batch_ab.txt).  GSA_SCORE_K = 2 / 4 forces one
+    const int scoreK = kenv == 2 ? 2 : 4;
+    if (work.empty())
+    {
+        if (krow)
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, 0);  // nothing to launch
+            li.ns = gsa::kSparseNS;
+            li.k = scoreK;
+            li.npairs = npairs;
+        }
+        return GSA_SUCCESS;
+    }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax;
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+    }
+    // the batch's pairs (bp: indices into pairs) and those that run alone
+    const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
+    std::vector<int> bp, alone;
+    std::vector<gsa::PairDesc> hd;
+    long long tickets = 0, gran = 0;
+    for (int p : work)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        bool stripOk = false;
+        int s = score_ranges(R, C, smax, gapo, gape, local, &stripOk);
+        if (s != GSA_SUCCESS) return s;
+        if (!krow || !stripOk)
+        {
+            alone.push_back(p);
+            continue;
+        }
+        gsa::PairDesc d;
+        std::memset(&d, 0, sizeof(d));
+        d.seqY = pairs[p].seqY;
+        d.seqX = pairs[p].seqX;
+        d.R = (int)R;
+        d.C = (int)C;
+        d.Cp = (int)C;
+        d.nTickets = (int)((R + TR - 1) / TR);
+        d.ticketBase = (int)tickets;
+        d.granOff = gran;
+        tickets += d.nTickets;
+        gran += (long long)d.nTickets * gsa::gran_stride(d.Cp);
+        if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+        bp.push_back(p);
+        hd.push_back(d);
+    }
+    float ms = 0.f;
+    if (!bp.empty())
+    {
+        const int nb = (int)bp.size();
+        const std::vector<int> sched = batch_schedule(ctx, hd, tickets);
+        int s = stage_descs(ctx, hd, sched, st);
+        if (s != GSA_SUCCESS) return s;
+        if ((s = ensure_gran(ctx, 2 * (size_t)gran, st)) != GSA_SUCCESS) return s;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
+        // two result words per pair, then the decoded answers and the error word's
+        const size_t resBytes = (size_t)nb * 2 * sizeof(unsigned long long);
+        const size_t outBytes = ((size_t)nb + 1) * sizeof(gsa::ScoreOut);
+        if ((s = reserve_hard(ctx, ctx->buf[kBufSbatch], resBytes + outBytes, 4096)) != GSA_SUCCESS) return s;
+        gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
+        unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+        unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+        unsigned long long* const res = ctx->buf[kBufSbatch].as<unsigned long long>();
+        gsa::ScoreOut* const dout = (gsa::ScoreOut*)(ctx->buf[kBufSbatch].as<char>() + resBytes);
+        gsa::StripArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.subst = subst;
+        a.substsz = substsz;
+        a.g = gapo;
+        a.go = gapo;
+        a.ge = gape;
+        a.ns = gsa::kSparseNS;
+        a.pairs = ddesc;
+        a.nPairs = nb;
+        a.nTicketsTotal = (int)tickets;
+        a.sched = sched.empty() ? nullptr : (const int*)(ddesc + nb);
+        a.gran = dgran;
+        a.gran2 = dgran + gran;
+        a.ticket = ctx->ctl;
+        a.err = (unsigned*)(sctl + 3);  // the score kernels' own error word (score_ag_strip)
+        a.spin = ctx->spin_ticks;
+        a.swBest = res;  // a batch: the base of the pairs' result words
+        if (nb == 1)
+        {
+            // one pair left: the kernel's single-pair form, its words laid out as a batch's pair 0
+            a.agResult = (int*)res;
+            a.swBest = res + 1;
+            a.idxBits = sw_idx_bits(hd[0].R, hd[0].C);
+        }
+        a.epoch = ++ctx->epoch;
+        if (a.epoch == 0) a.epoch = ++ctx->epoch;
+        if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess ||
+            (e = hipMemsetAsync(res, 0, resBytes, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        (void)hipEventRecord(ctx->ev0, st);
+        const int mode = local ? (gapo == gape ? gsa::kModeScoreSWL : gsa::kModeScoreSW)
+                               : (gapo == gape ? gsa::kModeScoreAGL : gsa::kModeScoreAG);
+        // the int8 column profile for NW-LG only: at 4 rows per lane it gains there (512 pairs: 31.5 ->
+        // 29.1 ms), costs NW-AG (49.5 -> 54.3 ms) and leaves SW-LG where it is (47.3 / 47.2;
+        // profiles/score_batch_ab.txt).  GSA_KROW_Q8=0 / 2: int16 / int8 always
+        const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+        a.q8 = (q8env != 0 && (q8env == 2 || mode == gsa::kModeScoreAGL) &&
+                gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+        a.q8flag = ctx->ctl + 2;
+        // one pair: one workgroup per CU (its tickets are a chain); a batch: all resident slots
+        const int grid = nb == 1 ? std::max(1, std::min((int)tickets, ctx->cu_count)) : 0;
+        if ((e = gsa::launch_krow_score(a, mode, scoreK, grid, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        if ((e = gsa::launch_score_finalize(ddesc, nb, res, a.err, local != 0, dout, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_KROW, st, a.epoch);
+            li.ns = a.ns;
+            li.k = scoreK;
+            li.q8 = a.q8;
+            li.npairs = npairs;
+            li.pair_major = (nb > 1 && sched.empty()) ? 1 : 0;
+            li.tickets = tickets;
+        }
+        (void)hipEventRecord(ctx->ev1, st);
+        std::vector<gsa::ScoreOut> ho((size_t)nb + 1);
+        if ((e = hipMemcpyAsync(ho.data(), dout, outBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+        const unsigned err = (unsigned)ho[(size_t)nb].score;
+        if (err != 0 && err != 2u) return GSA_ERROR_KERNEL_FAILURE;
+        for (int i = 0; i < nb; ++i)
+        {
+            const gsa::ScoreOut& o = ho[(size_t)i];
+            // a table outside int16 after the shift (every pair), or a pair's score >= 2^26: alone
+            if (err == 2u || o.status != 0)
+            {
+                alone.push_back(bp[(size_t)i]);
+                continue;
+            }
+            gsa_score_result& r = out[bp[(size_t)i]];
+            r.score = o.score;
+            r.i_end = o.i_end;
+            r.j_end = o.j_end;
+        }
+    }
+    for (int p : alone)
+    {
+        int s = score_dev_impl(ctx, pairs[p].seqY, pairs[p].adjrows, pairs[p].seqX, pairs[p].adjcols, subst, substsz, gapo,
+                               gape, local, &out[p], st, smax);
+        if (s != GSA_SUCCESS) return s;
+        ms += out[p].calc_kernel_ms;
+        out[p].calc_kernel_ms = 0.f;
+    }
+    if (batch_ms) *batch_ms = ms;
+    return GSA_SUCCESS;
+}
+
+// Longest subject the database search sends to the lane kernel (GSA_DB_MAXC overrides it): the largest
+// length of the sweep of tools/score_db_bench.py at which that kernel still beat the batched K-rows
+// path in all three modes (profiles/score_db_ab.txt).  Measured: it won at every swept
+// length, 64 ... 4096 (1.4-1.9x), so this is the sweep's upper end, not a crossover.
+constexpr int kDbLanesLmax = 4096;
+
+// gsa_score_db_dev: empty pairs on the host, the subjects the lane kernel does not take through
+// score_batch_impl (first, so that gsa_last_launch reports the lane launch), the others, longest
+// first, four to a wave task in one launch of nw_lanes.hip.
+int score_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                  int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                  gsa_score_result* out, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !query || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    if (nsubj < 1 || adjq < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (db_off[0] < 0) return GSA_ERROR_INVALID_VALUE;
+    for (int s = 0; s < nsubj; ++s)
+        if (db_off[s + 1] <= db_off[s] || db_off[s + 1] - db_off[s] > (int64_t)INT32_MAX) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    auto pair_of = [&](int s) {
+        gsa_pair_dev p;
+        std::memset(&p, 0, sizeof(p));
+        p.seqY = query;
+        p.adjrows = adjq;
+        p.seqX = db + db_off[s];
+        p.adjcols = (int32_t)(db_off[s + 1] - db_off[s]);
+        return p;
+    };
+    if (env_int(ctx, "GSA_DB_LANES", 1) == 0)
+    {
+        std::vector<gsa_pair_dev> pairs((size_t)nsubj);
+        for (int s = 0; s < nsubj; ++s) pairs[(size_t)s] = pair_of(s);
+        return score_batch_impl(ctx, nsubj, pairs.data(), subst, substsz, gapo, gape, local, out, kernel_ms, st);
+    }
+    const int64_t R = adjq - 1;
+    // empty pairs: one boundary, nothing to fill (score_batch_impl's rule)
+    std::vector<int> work;
+    for (int s = 0; s < nsubj; ++s)
+    {
+        const int64_t C = db_off[s + 1] - db_off[s] - 1;
+        out[s].calc_kernel_ms = 0.f;
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            out[s].score = (local || k == 0) ? 0 : (int32_t)(gapo + (k - 1) * gape);
+            out[s].i_end = local ? 0 : R;
+            out[s].j_end = local ? 0 : C;
+        }
+        else
+            work.push_back(s);
+    }
+    if (work.empty()) return GSA_SUCCESS;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax;
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+    }
+    const int lmax = std::max(0, std::min(env_int(ctx, "GSA_DB_MAXC", kDbLanesLmax), gsa::kDbLanesMaxC));
+    // the query's profile must fit LDS (else every subject takes the other path)
+    const bool fits = R < (1 << 20) && gsa::dblanes_lds_bytes((int)R, substsz) <= (size_t)ctx->lds_max;
+    std::vector<int> lanes, other;
+    for (int s : work)
+    {
+        const int64_t C = db_off[s + 1] - db_off[s] - 1;
+        bool stripOk = false;
+        int st2 = score_ranges(R, C, smax, gapo, gape, local, &stripOk);
+        if (st2 != GSA_SUCCESS) return st2;
+        // local: a row's best key packs the score above 13 column bits
+        const bool keyOk = !local || smax * std::min(R, C) < gsa::kDbLanesMaxScore;
+        (fits && C <= lmax && keyOk ? lanes : other).push_back(s);
+    }
+    float ms = 0.f;
+    if (!other.empty())
+    {
+        std::vector<gsa_pair_dev> pairs(other.size());
+        std::vector<gsa_score_result> res(other.size());
+        for (size_t k = 0; k < other.size(); ++k) pairs[k] = pair_of(other[k]);
+        int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local, res.data(),
+                                 &ms, st);
+        if (s != GSA_SUCCESS) return s;
+        for (size_t k = 0; k < other.size(); ++k) out[other[k]] = res[k];
+    }
+    if (!lanes.empty())
+    {
+        // longest first: a task's four subjects are of like length, and the long tasks start first
+        std::stable_sort(lanes.begin(), lanes.end(), [&](int x, int y) {
+            return db_off[x + 1] - db_off[x] > db_off[y + 1] - db_off[y];
+        });
+        const size_t n = lanes.size();
+        const int ntasks = (int)((n + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+        const int cmax = (int)(db_off[lanes[0] + 1] - db_off[lanes[0]] - 1);
+        const int passes = (int)((R + gsa::kDbLanesPassRows - 1) / gsa::kDbLanesPassRows);
+        std::vector<long long> hoff(n);
+        std::vector<int> hlen(n);
+        for (size_t k = 0; k < n; ++k)
+        {
+            hoff[k] = (long long)db_off[lanes[k]];
+            hlen[k] = (int)(db_off[lanes[k] + 1] - db_off[lanes[k]] - 1);
+        }
+        // [counter, 64 B][offsets][lengths][results]
+        const size_t offAt = 64, lenAt = offAt + n * 8, outAt = (lenAt + n * 4 + 15) / 16 * 16;
+        const size_t bytes = outAt + n * sizeof(gsa::DbLanesOut);
+        int s = reserve_hard(ctx, ctx->buf[kBufDbl], bytes, 4096);
+        if (s != GSA_SUCCESS) return s;
+        int wgs = 1;
+        if ((e = gsa::dblanes_resident((int)R, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        const int grid = std::max(1, std::min(wgs, (ntasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+        const int bndStride = cmax + 1;
+        if (passes > 1)
+        {
+            // per resident wave and subject slot, (H, F) by column: bounded by the waves, not the database
+            const size_t bb = (size_t)grid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)bndStride * sizeof(int2);
+            if ((s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bb, 4096)) != GSA_SUCCESS) return s;
+        }
+        char* const base = ctx->buf[kBufDbl].as<char>();
+        gsa::DbLanesArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.query = query;
+        a.db = db;
+        a.subst = subst;
+        a.substsz = substsz;
+        a.go = gapo;
+        a.ge = gape;
+        a.R = (int)R;
+        a.passes = passes;
+        a.nsubj = (int)n;
+        a.ntasks = ntasks;
+        a.off = (const long long*)(base + offAt);
+        a.len = (const int*)(base + lenAt);
+        a.out = (gsa::DbLanesOut*)(base + outAt);
+        a.counter = (unsigned*)base;
+        a.bnd = passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
+        a.bndStride = bndStride;
+        if ((e = hipMemsetAsync(base, 0, 64, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(base + offAt, hoff.data(), n * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(base + lenAt, hlen.data(), n * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        (void)hipEventRecord(ctx->ev0, st);
+        if ((e = gsa::launch_dblanes(a, local, grid, nullptr, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventRecord(ctx->ev1, st);
+        note_launch(ctx);
+        {
+            gsa_launch_info& li = new_launch_info(ctx, GSA_LAUNCH_SCORE_LANES, st, 0);
+            li.ns = gsa::kDbLanesWaves;
+            li.k = gsa::kDbLanesKQ;
+            li.npairs = (int32_t)n;
+            li.tickets = ntasks;
+        }
+        std::vector<gsa::DbLanesOut> ho(n);
+        if ((e = hipMemcpyAsync(ho.data(), a.out, n * sizeof(gsa::DbLanesOut), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        float lms = 0.f;
+        (void)hipEventElapsedTime(&lms, ctx->ev0, ctx->ev1);
+        ms += lms;
+        for (size_t k = 0; k < n; ++k)
+        {
+            gsa_score_result& r = out[lanes[k]];
+            r.score = ho[k].score;
+            r.i_end = ho[k].i_end;
+            r.j_end = ho[k].j_end;
+            r.calc_kernel_ms = 0.f;
+        }
+    }
+    if (kernel_ms) *kernel_ms = ms;
+    return GSA_SUCCESS;
+}
+
+// Default of gsa_align_db_dev's scratch_limit: bytes of move codes a call holds at once.
+constexpr int64_t kAlignDbScratch = 256ll << 20;
+
+// The move bytes of a walk (last move first) as a CIGAR: forward order, run-length encoded.
+std::string fold_cigar(const unsigned char* mv, int64_t n)
+{
+    std::string s;
+    for (int64_t k = n - 1; k >= 0;)
+    {
+        const unsigned char op = mv[k];
+        int64_t run = 0;
+        while (k >= 0 && mv[k] == op)
+        {
+            ++run;
+            --k;
+        }
+        char dig[24];
+        int nd = 0;
+        for (int64_t v = run; v > 0; v /= 10) dig[nd++] = (char)('0' + v % 10);
+        while (nd > 0) s += dig[--nd];
+        s += (char)op;
+    }
+    return s;
+}
+
+// gsa_align_db_dev: hits with an empty side on the host; the hits the trace kernels take, longest
+// first, in chunks whose move codes fit scratch_limit, a fill and a walk launch per chunk and one copy
+// of the results and move bytes back (nw_lanes_trace.hip); the others (status 1) through
+// score_batch_impl for their score and end cell.  gsa_last_launch's record is left as it was.
+int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                  int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
+                  int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
+                  char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info, float* kernel_ms,
+                  hipStream_t st)
+{
+    if (!ctx || !query || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    if (nsubj < 1 || adjq < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (nhits < 0 || scratch_limit < 0 || cigar_cap < 0) return GSA_ERROR_INVALID_VALUE;
+    if ((nhits > 0 && !hits) || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (db_off[0] < 0) return GSA_ERROR_INVALID_VALUE;
+    for (int s = 0; s < nsubj; ++s)
+        if (db_off[s + 1] <= db_off[s] || db_off[s + 1] - db_off[s] > (int64_t)INT32_MAX) return GSA_ERROR_INVALID_VALUE;
+    for (int h = 0; h < nhits; ++h)
+        if (hits[h] < 0 || hits[h] >= nsubj) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_db_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t R = adjq - 1;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax = 1;
+    if (R > 0)
+    {
+        // gsa_score_db_dev's range test, over the whole database: the same calls are rejected
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+        for (int s = 0; s < nsubj; ++s)
+        {
+            const int64_t C = db_off[s + 1] - db_off[s] - 1;
+            bool stripOk = false;
+            if (C > 0 && score_ranges(R, C, smax, gapo, gape, local, &stripOk) != GSA_SUCCESS)
+                return GSA_ERROR_INVALID_VALUE;
+        }
+    }
+    if (nhits == 0) return GSA_SUCCESS;
+
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : kAlignDbScratch;
+    const bool fits = R < (1 << 20) && gsa::dblanes_lds_bytes((int)R, substsz) <= (size_t)ctx->lds_max;
+    std::vector<std::string> cig((size_t)nhits);
+    std::vector<int> lanes, other;
+    for (int h = 0; h < nhits; ++h)
+    {
+        const int64_t C = db_off[hits[h] + 1] - db_off[hits[h]] - 1;
+        gsa_align_db_result& r = out[h];
+        std::memset(&r, 0, sizeof(r));
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            if (!local && k > 0)
+            {
+                r.score = (int32_t)(gapo + (k - 1) * gape);
+                r.i_end = R;
+                r.j_end = C;
+                cig[(size_t)h] = std::to_string(k) + (R > 0 ? 'I' : 'D');
+            }
+            continue;
+        }
+        const bool keyOk = !local || smax * std::min(R, C) < gsa::kDbLanesMaxScore;
+        // the fill keeps 4 x value + source: |H| <= smax min(R, C) + |go| + (R + C) |ge| (score_ranges' bound)
+        const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+        const bool take = fits && C <= gsa::kDbLanesMaxC && keyOk && valOk && gsa::dbtrace_code_bytes(R, C) <= limit;
+        (take ? lanes : other).push_back(h);
+    }
+    auto len_of = [&](int h) { return db_off[hits[h] + 1] - db_off[hits[h]] - 1; };
+    float fill_ms = 0.f, walk_ms = 0.f, other_ms = 0.f;
+    if (!lanes.empty())
+    {
+        // longest first: a task's four hits are of like length, and the long tasks start first
+        std::stable_sort(lanes.begin(), lanes.end(), [&](int x, int y) { return len_of(x) > len_of(y); });
+        // chunks [first, last) whose codes fit the limit; the largest of every buffer over the chunks
+        std::vector<std::pair<size_t, size_t>> chunks;
+        size_t maxN = 0;
+        int64_t maxCodes = 0, maxMoves = 0;
+        for (size_t b = 0; b < lanes.size();)
+        {
+            size_t k = b;
+            int64_t cb = 0, mb = 0;
+            while (k < lanes.size() && cb + gsa::dbtrace_code_bytes(R, len_of(lanes[k])) <= limit)
+            {
+                cb += gsa::dbtrace_code_bytes(R, len_of(lanes[k]));
+                mb += R + len_of(lanes[k]);
+                ++k;
+            }
+            chunks.emplace_back(b, k);
+            maxN = std::max(maxN, k - b);
+            maxCodes = std::max(maxCodes, cb);
+            maxMoves = std::max(maxMoves, mb);
+            b = k;
+        }
+        const int passes = (int)((R + gsa::kDbLanesPassRows - 1) / gsa::kDbLanesPassRows);
+        const int cmax = (int)len_of(lanes[0]);
+        int wgs = 1;
+        if ((e = gsa::dbtrace_resident((int)R, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        const int maxTasks = (int)((maxN + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+        const int maxGrid = std::max(1, std::min(wgs, (maxTasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+        // meta: [counter, 64 B][offsets][code offsets][move offsets][lengths][fill results]
+        const size_t offAt = 64, coffAt = offAt + maxN * 8, moffAt = coffAt + maxN * 8, lenAt = moffAt + maxN * 8;
+        const size_t foutAt = (lenAt + maxN * 4 + 15) / 16 * 16;
+        const size_t metaBytes = foutAt + maxN * sizeof(gsa::DbLanesOut);
+        // results: [walk results][move bytes]
+        const size_t movAt = maxN * sizeof(gsa::DbTraceOut);
+        const size_t resBytes = movAt + (size_t)maxMoves;
+        int s;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufAdbMeta], metaBytes, 4096)) != GSA_SUCCESS ||
+            (s = reserve_hard(ctx, ctx->buf[kBufAdbRes], resBytes, 4096)) != GSA_SUCCESS ||
+            (s = reserve_hard(ctx, ctx->buf[kBufAdbCodes], (size_t)maxCodes, 4096)) != GSA_SUCCESS)
+            return s;
+        if (passes > 1)
+        {
+            const size_t bb = (size_t)maxGrid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)(cmax + 1) * sizeof(int2);
+            if ((s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bb, 4096)) != GSA_SUCCESS) return s;
+        }
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        char* const meta = ctx->buf[kBufAdbMeta].as<char>();
+        unsigned char* const adbres = ctx->buf[kBufAdbRes].as<unsigned char>();
+        std::vector<char> hmeta(lenAt + maxN * 4), hres(resBytes);
+        for (const auto& ch : chunks)
+        {
+            const size_t n = ch.second - ch.first;
+            const int ntasks = (int)((n + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+            const int grid = std::max(1, std::min(wgs, (ntasks + gsa::kDbLanesWaves - 1) / gsa::kDbLanesWaves));
+            std::memset(hmeta.data(), 0, 64);
+            long long* const hoff = (long long*)(hmeta.data() + offAt);
+            long long* const hcoff = (long long*)(hmeta.data() + coffAt);
+            long long* const hmoff = (long long*)(hmeta.data() + moffAt);
+            int* const hlen = (int*)(hmeta.data() + lenAt);
+            int64_t cb = 0, mb = 0;
+            for (size_t k = 0; k < n; ++k)
+            {
+                const int h = lanes[ch.first + k];
+                hoff[k] = (long long)db_off[hits[h]];
+                hlen[k] = (int)len_of(h);
+                hcoff[k] = cb;
+                hmoff[k] = mb;
+                cb += gsa::dbtrace_code_bytes(R, hlen[k]);
+                mb += R + hlen[k];
+            }
+            gsa::DbTraceArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.fill.query = query;
+            a.fill.db = db;
+            a.fill.subst = subst;
+            a.fill.substsz = substsz;
+            a.fill.go = gapo;
+            a.fill.ge = gape;
+            a.fill.R = (int)R;
+            a.fill.passes = passes;
+            a.fill.nsubj = (int)n;
+            a.fill.ntasks = ntasks;
+            a.fill.off = (const long long*)(meta + offAt);
+            a.fill.len = (const int*)(meta + lenAt);
+            a.fill.out = (gsa::DbLanesOut*)(meta + foutAt);
+            a.fill.counter = (unsigned*)meta;
+            a.fill.bnd = passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
+            a.fill.bndStride = cmax + 1;
+            a.codes = ctx->buf[kBufAdbCodes].as<unsigned char>();
+            a.codeOff = (const long long*)(meta + coffAt);
+            a.moveOff = (const long long*)(meta + moffAt);
+            a.res = (gsa::DbTraceOut*)adbres;
+            a.moves = adbres + movAt;
+            a.local = local;
+            if ((e = hipMemcpyAsync(meta, hmeta.data(), hmeta.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            if ((e = gsa::launch_dbtrace(a, grid, ctx->adbev, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            note_launch(ctx);
+            if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)mb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            float m0 = 0.f, m1 = 0.f;
+            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+            fill_ms += m0;
+            walk_ms += m1;
+            const gsa::DbTraceOut* const ho = (const gsa::DbTraceOut*)hres.data();
+            for (size_t k = 0; k < n; ++k)
+            {
+                const int h = lanes[ch.first + k];
+                gsa_align_db_result& r = out[h];
+                r.score = ho[k].score;
+                r.i_start = ho[k].i_start;
+                r.j_start = ho[k].j_start;
+                r.i_end = ho[k].i_end;
+                r.j_end = ho[k].j_end;
+                if (ho[k].moves < 0 || ho[k].moves > R + hlen[k]) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                cig[(size_t)h] = fold_cigar((const unsigned char*)hres.data() + movAt + hmoff[k], ho[k].moves);
+            }
+            inf.chunks += 1;
+            inf.tasks += ntasks;
+            inf.code_bytes = std::max<int64_t>(inf.code_bytes, cb);
+        }
+        inf.lane_hits = (int32_t)lanes.size();
+    }
+    if (!other.empty())
+    {
+        // score and end cell from the score path; its launch record is not this call's to leave
+        const gsa_launch_info ll = ctx->ll;
+        const hipStream_t lls = ctx->ll_stream;
+        const unsigned e0 = ctx->ll_epoch0, e1 = ctx->ll_epoch;
+        std::vector<gsa_pair_dev> pairs(other.size());
+        std::vector<gsa_score_result> res(other.size());
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            gsa_pair_dev& p = pairs[k];
+            std::memset(&p, 0, sizeof(p));
+            p.seqY = query;
+            p.adjrows = adjq;
+            p.seqX = db + db_off[hits[other[k]]];
+            p.adjcols = (int32_t)(len_of(other[k]) + 1);
+        }
+        const int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local,
+                                       res.data(), &other_ms, st);
+        ctx->ll = ll;
+        ctx->ll_stream = lls;
+        ctx->ll_epoch0 = e0;
+        ctx->ll_epoch = e1;
+        if (s != GSA_SUCCESS) return s;
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            gsa_align_db_result& r = out[other[k]];
+            r.score = res[k].score;
+            r.i_end = res[k].i_end;
+            r.j_end = res[k].j_end;
+            r.status = 1;
+        }
+        inf.unsupported = (int32_t)other.size();
+    }
+    // the strings back to back in hit order; a hit's offset does not depend on the buffer's size
+    int64_t at = 0;
+    for (int h = 0; h < nhits; ++h)
+    {
+        gsa_align_db_result& r = out[h];
+        const int64_t len = (int64_t)cig[(size_t)h].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)h].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+    }
+    if (cigar_need) *cigar_need = at;
+    inf.fill_ms = fill_ms;
+    inf.walk_ms = walk_ms;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = fill_ms + walk_ms + other_ms;
+    return GSA_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                     int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
+                     char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info, float* kernel_ms,
+                     void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_db_impl(ctx, query, adjq, db, db_off, nsubj, hits, nhits, subst, substsz, gapo, gape, local,
+                         scratch_limit, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                        int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_kernel_ms,
+                        void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, local, out, batch_kernel_ms,
+                            pick_stream(ctx, stream));
+}
+
+int gsa_score_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
+                     int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                     gsa_score_result* out, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_db_impl(ctx, query, adjq, db, db_off, nsubj, subst, substsz, gapo, gape, local, out, kernel_ms,
+                         pick_stream(ctx, stream));
+}
+
+int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                  const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                  gsa_score_result* out, void* stream)
+{
+    return score_dev_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, local, out,
+                          pick_stream(ctx, stream), -1);
+}
+
+int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+              const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+              gsa_score_result* out, gsa_laps* laps)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    gsa_laps L {};
+    auto t = Clock::now();
+    if ((s = ensure_dev(ctx, 0, (size_t)adjrows * 4)) || (s = ensure_dev(ctx, 1, (size_t)adjcols * 4)) ||
+        (s = ensure_dev(ctx, 2, (size_t)substsz * substsz * 4)))
+        return s;
+    L.alloc = ms_since(t);
+    lap(ctx, "align.alloc");
+    hipError_t e;
+    if ((e = hipMemcpyAsync(ctx->buf[kBufIo0].p, seqY, (size_t)adjrows * 4, hipMemcpyHostToDevice, ctx->stream)) ||
+        (e = hipMemcpyAsync(ctx->buf[kBufIo1].p, seqX, (size_t)adjcols * 4, hipMemcpyHostToDevice, ctx->stream)) ||
+        (e = hipMemcpyAsync(ctx->buf[kBufIo2].p, subst, (size_t)substsz * substsz * 4, hipMemcpyHostToDevice, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    L.cpy_dev = ms_since(t);
+    lap(ctx, "align.cpy_dev");
+    s = score_dev_impl(ctx, ctx->buf[kBufIo0].as<const int32_t>(), adjrows, ctx->buf[kBufIo1].as<const int32_t>(), adjcols,
+                       ctx->buf[kBufIo2].as<const int32_t>(), substsz, gapo, gape, local, out, ctx->stream,
+                       subst_absmax(subst, substsz));
+    if (s != GSA_SUCCESS) return s;
+    L.calc = ms_since(t);
+    lap(ctx, "align.calc");
+    L.calc_kernel_ms = out->calc_kernel_ms;
+    if (laps) *laps = L;
+    return GSA_SUCCESS;
+}
+
+}  // extern "C"

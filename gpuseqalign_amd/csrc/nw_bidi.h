@@ -1,4 +1,4 @@
-// nw_bidi.h -- score-only NW from both ends (gsa_capi.hip score_bidi): the pair's top half runs
+// nw_bidi.h -- score-only NW from both ends (gsa_score.hip score_bidi): the pair's top half runs
 // forward and its bottom half, reversed, runs forward in the same launch on other CUs (tickets
 // interleaved, StripArgs::bidiTop); each half taps the row where the halves meet
 // (StripArgs::tapRow / tapRowB), and a combine kernel takes the best crossing.

@@ -1,5 +1,5 @@
 // nw_lanes.h -- database search, score-only: one query against many short subjects, every subject on
-// a group of lanes of one wave (nw_lanes.hip); used by gsa_capi.hip.
+// a group of lanes of one wave (nw_lanes.hip); used by gsa_score.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

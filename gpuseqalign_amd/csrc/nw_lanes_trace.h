@@ -1,5 +1,5 @@
 // nw_lanes_trace.h -- database search, alignments of chosen hits: the lane kernel's fill with 4-bit
-// move codes and the walk over them (nw_lanes_trace.hip); used by gsa_capi.hip.
+// move codes and the walk over them (nw_lanes_trace.hip); used by gsa_score.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

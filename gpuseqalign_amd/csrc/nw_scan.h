@@ -1,4 +1,4 @@
-// nw_scan.h -- score-only NW / SW with linear or affine gaps (nw_scan.hip); used by gsa_capi.hip.
+// nw_scan.h -- score-only NW / SW with linear or affine gaps (nw_scan.hip); used by gsa_score.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -198,7 +198,7 @@ def test_profile_widths_and_stale_columns(engine, golden, monkeypatch, q8, k, go
 @pytest.mark.parametrize("q8", ["0", "1"])
 @pytest.mark.parametrize("go,ge,local", MODES)
 def test_score_both_ends(engine, golden, monkeypatch, k, q8, go, ge, local, knobs):
-    """NW from both ends (gsa_capi.hip score_bidi, nw_bidi.hip), forced at every size
+    """NW from both ends (gsa_score.hip score_bidi, nw_bidi.hip), forced at every size
     (GSA_SCORE_BIDI=2; by default pairs whose halves keep >= 4 tickets): the top half's tap row m,
     the reversed bottom half's row R - m and the combine.  Local modes with R % K == 0 take the
     three-pair SW from both ends (GSA_SCORE_BIDI_SW defaults to on); R % K != 0 keeps the
