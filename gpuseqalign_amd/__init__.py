@@ -133,6 +133,23 @@ class AlignDbInfo(ctypes.Structure):
                 ("walk_ms", ctypes.c_float)]
 
 
+class DbHit(ctypes.Structure):
+    """gsa_db_hit (include/gsa.h): one ranked subject of a query of gsa_score_db_multi_dev."""
+    _fields_ = [("subject", ctypes.c_int32), ("score", ctypes.c_int32), ("i_end", ctypes.c_int32),
+                ("j_end", ctypes.c_int32)]
+
+
+class ScoreDbMultiInfo(ctypes.Structure):
+    """gsa_score_db_multi_info (include/gsa.h): what the last gsa_score_db_multi_dev call ran."""
+    _fields_ = [("lane_queries", ctypes.c_int32), ("other_queries", ctypes.c_int32), ("launches", ctypes.c_int32),
+                ("workgroups", ctypes.c_int32), ("lane_pairs", ctypes.c_int64), ("units", ctypes.c_int64),
+                ("profile_builds", ctypes.c_int64), ("result_bytes", ctypes.c_int64), ("lanes_ms", ctypes.c_float),
+                ("select_ms", ctypes.c_float)]
+
+
+# numpy view of DbHit: the records of Engine.score_db_multi_dev's "hits"
+DB_HIT_DTYPE = np.dtype([("subject", np.int32), ("score", np.int32), ("i_end", np.int32), ("j_end", np.int32)])
+
 _LAPFN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_char_p)  # gsa_lap_fn
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
@@ -203,6 +220,11 @@ SIGNATURES = {
                                         _i32, _i32, _i64, ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
                                         ctypes.POINTER(_i64), ctypes.POINTER(AlignDbInfo),
                                         ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_db_multi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32, _vp,
+                                              _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
+                                              ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
+                                              ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_db_multi_unit": (_i32, []),
     "gsa_score":(ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -245,6 +267,11 @@ def _p(a: np.ndarray):
 
 def _c32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def score_db_multi_unit() -> int:
+    """Wave tasks (of four subjects) in a unit of gsa_score_db_multi_dev."""
+    return int(lib().gsa_score_db_multi_unit())
 
 
 def sparse_tile_by() -> int:
@@ -649,6 +676,87 @@ class Engine:
         if not order:
             return []
         return list(zip(order, self.align_db(query, subjects, order, subst, gapo, gape, local)))
+
+    # -- many queries against one database in one call ----------------------
+
+    def score_db_multi_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, subst_ptr: int, substsz: int,
+                           gapo: int, gape: Optional[int] = None, local: bool = False, top: int = 0,
+                           want_scores: bool = True, max_workgroups: int = 0, scratch_limit: int = 0,
+                           stream: Optional[int] = None) -> dict:
+        """Many queries against a database (gsa_score_db_multi_dev; synchronous): the queries in one
+        device buffer `queries_ptr` with host offsets `q_off`, as `db_ptr` and `db_off` hold the
+        subjects.  {"scores": int32 array [nq, nsubj] (None unless want_scores), "hits": structured
+        array [nq, min(top, nsubj)] of (subject, score, i_end, j_end), every query's best subjects by
+        (score descending, subject ascending), ranked on the device (None when top is 0),
+        "kernel_ms"}.  Every pair's result is score_db_dev's for that query and subject.
+        `max_workgroups` caps the lane kernel's grid (0: all resident), `scratch_limit` the bytes of
+        results held on the device at once (0: the default).  last_score_db_multi_info() says what ran."""
+        qo = np.ascontiguousarray(q_off, dtype=np.int64)
+        off = np.ascontiguousarray(db_off, dtype=np.int64)
+        nq, n = len(qo) - 1, len(off) - 1
+        top = int(top)
+        ntop = min(top, n) if top > 0 else 0
+        scores = np.empty((max(nq, 0), max(n, 0)), dtype=np.int32) if want_scores else None
+        hits = np.zeros((max(nq, 0), max(ntop, 0)), dtype=DB_HIT_DTYPE) if top > 0 else None
+        info = ScoreDbMultiInfo()
+        ms = ctypes.c_float(0.0)
+        i64p = ctypes.POINTER(_i64)
+        st = lib().gsa_score_db_multi_dev(
+            self._h, queries_ptr, qo.ctypes.data_as(i64p), nq, db_ptr, off.ctypes.data_as(i64p), n, subst_ptr, substsz,
+            gapo, gapo if gape is None else gape, int(local), top, int(max_workgroups), int(scratch_limit),
+            scores.ctypes.data_as(_i32p) if scores is not None else None,
+            hits.ctypes.data_as(ctypes.POINTER(DbHit)) if hits is not None else None, ctypes.byref(info),
+            ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_db_multi_dev")
+        self._score_db_multi_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                     for k, t in info._fields_}
+        return {"scores": scores, "hits": hits, "kernel_ms": float(ms.value)}
+
+    def last_score_db_multi_info(self) -> dict:
+        """gsa_score_db_multi_info of the last score_db_multi_dev call on this engine: "lane_queries",
+        "other_queries", "launches", "workgroups", "lane_pairs", "units", "profile_builds",
+        "result_bytes", "lanes_ms", "select_ms"."""
+        info = getattr(self, "_score_db_multi_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_score_db_multi_info: no score_db_multi_dev call yet")
+        return dict(info)
+
+    def score_db_multi(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
+                       top: int = 0) -> dict:
+        """score_db_multi_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front, as score_db takes them."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+
+        def pack(seqs):
+            seqs = [_c32(x) for x in seqs]
+            off = np.zeros(len(seqs) + 1, dtype=np.int64)
+            if seqs:
+                off[1:] = np.cumsum([len(x) for x in seqs])
+            return up(np.concatenate(seqs) if seqs else np.zeros(1, np.int32)), off
+
+        dS = up(subst.ravel())
+        (dQ, qoff), (dD, off) = pack(queries), pack(subjects)
+        torch.cuda.synchronize(dev)
+        return self.score_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
+                                       local, top)
+
+    def search_db_multi(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
+                        top: int = 10) -> list:
+        """Database search with alignments for many queries: one score_db_multi with `top`, then
+        align_db per query on its hits.  Per query [(subject_index, result dict)], equal to
+        [search_db(q, ...) for q in queries]."""
+        if max(int(top), 0) == 0:
+            return [[] for _ in queries]
+        hits = self.score_db_multi(queries, subjects, subst, gapo, gape, local, top)["hits"]
+        out = []
+        for q, row in zip(queries, hits):
+            order = [int(s) for s in row["subject"]]
+            out.append(list(zip(order, self.align_db(q, subjects, order, subst, gapo, gape, local))) if order else [])
+        return out
 
     # -- device-side verification (SURVEY.md 8(f)1) ---------------------------------------
 

@@ -1157,6 +1157,8 @@ void gsa_ctx_destroy(gsa_ctx* ctx)
     }
     for (hipEvent_t ev : ctx->adbev)
         if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->dbmev)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->ptev)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->ptstream) (void)hipStreamDestroy(ctx->ptstream);

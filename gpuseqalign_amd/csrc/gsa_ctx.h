@@ -146,6 +146,13 @@ enum BufId
     kBufAdbCodes,
     kBufAdbMeta,
     kBufAdbRes,
+    // many queries against a database (gsa_score_db_multi_dev): counters, the lane subjects' offsets,
+    // lengths and indices and a launch's queries; the result matrix of one chunk; the patches from the
+    // other paths, then the chunk's hits and compacted scores; the ranking's keys and sort storage
+    kBufDbmMeta,
+    kBufDbmOut,
+    kBufDbmRes,
+    kBufDbmSel,
     // mlsppt: host-mapped per-tile-row words (epoch << 32 | column chunks in memory); a pinned host
     // buffer (>= kPtPin) the strided column chunks are packed into by copies on ptstream
     kBufPtFlags,  // mapped host memory
@@ -212,6 +219,7 @@ struct gsa_ctx
     static constexpr size_t kPtPin = 64u << 20;  // two slots
     hipStream_t ptstream = nullptr;
     hipEvent_t adbev[3] = {nullptr, nullptr, nullptr};  // gsa_align_db_dev: around the fill and the walk
+    hipEvent_t dbmev[4] = {nullptr, nullptr, nullptr, nullptr};  // gsa_score_db_multi_dev: the lane launches, the ranking
     // copy-back of the host-buffer entry points into pageable caller memory: per copy thread a
     // stream and two pinned chunks (DMA of chunk k+1 overlaps the host copy of chunk k)
     static constexpr int kCopyThreads = 8;

@@ -1,7 +1,8 @@
 // gsa_score.hip -- the score-only and database entry points of libgsa.so (declared in include/gsa.h):
-// gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev and gsa_align_db_dev, on the K-rows
-// and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan (nw_scan.hip), NW / SW from both
-// ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip, nw_lanes_trace.hip).  The context
+// gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev, gsa_score_db_multi_dev and
+// gsa_align_db_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
+// (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
+// nw_lanes_multi.hip, nw_lanes_trace.hip).  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,7 @@
 #include "nw_bidi.h"
 #include "nw_krow.h"
 #include "nw_lanes.h"
+#include "nw_lanes_multi.h"
 #include "nw_lanes_trace.h"
 #include "nw_scan.h"
 #include "nw_strip.h"
@@ -953,6 +955,24 @@ int score_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
     return GSA_SUCCESS;
 }
 
+// gsa_last_launch's record, put back when the scope ends: the calls that report through an info
+// struct of their own leave it as it was, also when they run other entry points' paths.
+struct KeepLaunchRecord
+{
+    gsa_ctx* ctx;
+    gsa_launch_info ll;
+    hipStream_t st;
+    unsigned e0, e1;
+    explicit KeepLaunchRecord(gsa_ctx* c) : ctx(c), ll(c->ll), st(c->ll_stream), e0(c->ll_epoch0), e1(c->ll_epoch) {}
+    ~KeepLaunchRecord()
+    {
+        ctx->ll = ll;
+        ctx->ll_stream = st;
+        ctx->ll_epoch0 = e0;
+        ctx->ll_epoch = e1;
+    }
+};
+
 // Default of gsa_align_db_dev's scratch_limit: bytes of move codes a call holds at once.
 constexpr int64_t kAlignDbScratch = 256ll << 20;
 
@@ -1188,9 +1208,7 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
     if (!other.empty())
     {
         // score and end cell from the score path; its launch record is not this call's to leave
-        const gsa_launch_info ll = ctx->ll;
-        const hipStream_t lls = ctx->ll_stream;
-        const unsigned e0 = ctx->ll_epoch0, e1 = ctx->ll_epoch;
+        const KeepLaunchRecord keep(ctx);
         std::vector<gsa_pair_dev> pairs(other.size());
         std::vector<gsa_score_result> res(other.size());
         for (size_t k = 0; k < other.size(); ++k)
@@ -1204,10 +1222,6 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
         }
         const int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local,
                                        res.data(), &other_ms, st);
-        ctx->ll = ll;
-        ctx->ll_stream = lls;
-        ctx->ll_epoch0 = e0;
-        ctx->ll_epoch = e1;
         if (s != GSA_SUCCESS) return s;
         for (size_t k = 0; k < other.size(); ++k)
         {
@@ -1246,9 +1260,321 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
     return GSA_SUCCESS;
 }
 
+// Default of gsa_score_db_multi_dev's scratch_limit: bytes of result matrix a call holds at once.
+constexpr int64_t kDbMultiScratch = 256ll << 20;
+
+bool offsets_ok(const int64_t* off, int32_t n)
+{
+    if (off[0] < 0) return false;
+    for (int s = 0; s < n; ++s)
+        if (off[s + 1] <= off[s] || off[s + 1] - off[s] > (int64_t)INT32_MAX) return false;
+    return true;
+}
+
+// gsa_score_db_multi_dev: the queries in chunks of consecutive rows whose result matrix fits
+// scratch_limit.  Per chunk: the pairs of other paths first (empty sides on the host, subjects past
+// Lmax through score_batch_impl per query, whole queries through score_db_impl), then one launch of
+// nw_lanes_multi.hip per sweep class over the lane subjects (sorted longest first once, for all
+// queries), the other paths' results scattered into the matrix, the ranking, and one copy back.
+int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
+                        const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo,
+                        int32_t gape, int32_t local, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                        int32_t* scores, gsa_db_hit* hits, gsa_score_db_multi_info* info, float* kernel_ms,
+                        hipStream_t st)
+{
+    static_assert(sizeof(gsa_db_hit) == sizeof(gsa::DbMultiHit), "gsa_db_hit is the ranking's record");
+    if (!ctx || !queries || !q_off || !db || !db_off || !subst) return GSA_ERROR_INVALID_VALUE;
+    if (nq < 1 || nsubj < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (top < 0 || max_workgroups < 0 || scratch_limit < 0) return GSA_ERROR_INVALID_VALUE;
+    if (!scores && !hits) return GSA_ERROR_INVALID_VALUE;
+    if (!offsets_ok(q_off, nq) || !offsets_ok(db_off, nsubj)) return GSA_ERROR_INVALID_VALUE;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : kDbMultiScratch;
+    const int64_t rowBytes = (int64_t)nsubj * (int64_t)sizeof(gsa::DbLanesOut);
+    // rows of a chunk: within the limit, and few enough for 32-bit segment offsets in the ranking
+    const int64_t rowsMax = std::min<int64_t>(std::min<int64_t>(limit / rowBytes, (1ll << 30) / nsubj), nq);
+    if (rowsMax < 1) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    gsa_score_db_multi_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int ntop = std::min(top, nsubj);
+    const bool rank = hits && ntop > 0;
+
+    auto rows_of = [&](int q) { return q_off[q + 1] - q_off[q] - 1; };
+    auto cols_of = [&](int s) { return db_off[s + 1] - db_off[s] - 1; };
+    int64_t Rmax = 0, Cmax = 0;
+    for (int q = 0; q < nq; ++q) Rmax = std::max(Rmax, rows_of(q));
+    for (int s = 0; s < nsubj; ++s) Cmax = std::max(Cmax, cols_of(s));
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax = 1;
+    if (Rmax > 0 && Cmax > 0)
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+        // score_ranges' bounds grow with R and with C: the longest query against the longest subject
+        // is outside every kernel's range iff any pair is
+        bool stripOk = false;
+        const int s = score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
+        if (s != GSA_SUCCESS) return s;
+    }
+    const KeepLaunchRecord keep(ctx);
+
+    // the subjects: the lane kernel's, longest first; those with no letters; those past Lmax
+    const bool lanesOn = env_int(ctx, "GSA_DB_LANES", 1) != 0;
+    const int lmax = std::max(0, std::min(env_int(ctx, "GSA_DB_MAXC", kDbLanesLmax), gsa::kDbLanesMaxC));
+    std::vector<int> laneS, emptyS, longS;
+    for (int s = 0; s < nsubj; ++s)
+    {
+        const int64_t C = cols_of(s);
+        (C == 0 ? emptyS : C <= lmax ? laneS : longS).push_back(s);
+    }
+    std::stable_sort(laneS.begin(), laneS.end(), [&](int x, int y) { return cols_of(x) > cols_of(y); });
+    const size_t nl = laneS.size();
+    const int cmax = nl ? (int)cols_of(laneS[0]) : 0;
+    const int ntasks = (int)((nl + gsa::kDbLanesSubj - 1) / gsa::kDbLanesSubj);
+    const int unitsPerQuery = (ntasks + gsa::kDbMultiUnit - 1) / gsa::kDbMultiUnit;
+    // a query on the lane kernel: its profile fits LDS, and no lane subject is past the local key's bound
+    auto on_lanes = [&](int64_t R) {
+        if (!lanesOn || nl == 0 || R < 1 || R >= (1 << 20)) return false;
+        if (gsa::dblanes_lds_bytes((int)R, substsz) > (size_t)ctx->lds_max) return false;
+        return !local || smax * std::min<int64_t>(R, cmax) < gsa::kDbLanesMaxScore;
+    };
+    auto empty_pair = [&](int64_t R, int64_t C) {
+        const int64_t k = R + C;
+        return gsa::DbLanesOut {(local || k == 0) ? 0 : (int)(gapo + (k - 1) * gape), local ? 0 : (int)R, local ? 0 : (int)C, 0};
+    };
+
+    // meta: [unit counter, profile builds; 64 B][offsets][lengths][indices][a chunk's queries]
+    const size_t offAt = 64, lenAt = offAt + nl * 8, idxAt = lenAt + nl * 4, qAt = (idxAt + nl * 4 + 15) / 16 * 16;
+    const size_t metaBytes = qAt + (size_t)rowsMax * sizeof(gsa::DbMultiQuery);
+    int s = reserve_hard(ctx, ctx->buf[kBufDbmMeta], metaBytes, 4096);
+    if (s != GSA_SUCCESS) return s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufDbmOut], (size_t)(rowsMax * rowBytes), 4096)) != GSA_SUCCESS) return s;
+    size_t selBytes = 0, selTemp = 0;
+    if (rank)
+    {
+        if ((e = gsa::dbmulti_select_bytes((int)rowsMax, nsubj, &selBytes, &selTemp)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        if ((s = reserve_hard(ctx, ctx->buf[kBufDbmSel], selBytes, 4096)) != GSA_SUCCESS) return s;
+    }
+    for (hipEvent_t& ev : ctx->dbmev)
+        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    char* const meta = ctx->buf[kBufDbmMeta].as<char>();
+    gsa::DbLanesOut* const dout = ctx->buf[kBufDbmOut].as<gsa::DbLanesOut>();
+    {
+        std::vector<long long> hoff(nl);
+        std::vector<int> hlen(nl);
+        for (size_t k = 0; k < nl; ++k)
+        {
+            hoff[k] = (long long)db_off[laneS[k]];
+            hlen[k] = (int)cols_of(laneS[k]);
+        }
+        // (pageable sources: the copies have left the vectors when the calls return)
+        if ((e = hipMemsetAsync(meta, 0, 64, st)) != hipSuccess ||
+            (nl && ((e = hipMemcpyAsync(meta + offAt, hoff.data(), nl * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+                    (e = hipMemcpyAsync(meta + lenAt, hlen.data(), nl * 4, hipMemcpyHostToDevice, st)) != hipSuccess ||
+                    (e = hipMemcpyAsync(meta + idxAt, laneS.data(), nl * 4, hipMemcpyHostToDevice, st)) != hipSuccess)) ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    }
+
+    float lanes_ms = 0.f, all_ms = 0.f, select_ms = 0.f, other_ms = 0.f;
+    std::vector<gsa::DbMultiPatch> patches;
+    std::vector<gsa::DbMultiQuery> hq;
+    std::vector<gsa_pair_dev> pairs;
+    std::vector<gsa_score_result> res;
+    for (int64_t q0 = 0; q0 < nq; q0 += rowsMax)
+    {
+        const int64_t rows = std::min<int64_t>(rowsMax, nq - q0);
+        const int64_t npair = rows * nsubj;
+        patches.clear();
+        hq.clear();
+        auto patch = [&](int64_t row, int sidx, const gsa::DbLanesOut& v) {
+            patches.push_back(gsa::DbMultiPatch {row * nsubj + sidx, v});
+        };
+        for (int64_t row = 0; row < rows; ++row)
+        {
+            const int q = (int)(q0 + row);
+            const int64_t R = rows_of(q);
+            const int32_t* const query = queries + q_off[q];
+            if (R == 0)
+            {
+                for (int sj = 0; sj < nsubj; ++sj) patch(row, sj, empty_pair(0, cols_of(sj)));
+                continue;
+            }
+            if (!on_lanes(R))
+            {
+                res.resize((size_t)nsubj);
+                float ms = 0.f;
+                if ((s = score_db_impl(ctx, query, (int32_t)(R + 1), db, db_off, nsubj, subst, substsz, gapo, gape, local,
+                                       res.data(), &ms, st)) != GSA_SUCCESS)
+                    return s;
+                other_ms += ms;
+                for (int sj = 0; sj < nsubj; ++sj)
+                    patch(row, sj, gsa::DbLanesOut {res[(size_t)sj].score, (int)res[(size_t)sj].i_end, (int)res[(size_t)sj].j_end, 0});
+                inf.other_queries += 1;
+                continue;
+            }
+            hq.push_back(gsa::DbMultiQuery {(long long)q_off[q], (int)R, (int)row});
+            for (int sj : emptyS) patch(row, sj, empty_pair(R, 0));
+            if (!longS.empty())
+            {
+                pairs.resize(longS.size());
+                res.resize(longS.size());
+                for (size_t k = 0; k < longS.size(); ++k)
+                {
+                    gsa_pair_dev& p = pairs[k];
+                    std::memset(&p, 0, sizeof(p));
+                    p.seqY = query;
+                    p.adjrows = (int32_t)(R + 1);
+                    p.seqX = db + db_off[longS[k]];
+                    p.adjcols = (int32_t)(cols_of(longS[k]) + 1);
+                }
+                float ms = 0.f;
+                if ((s = score_batch_impl(ctx, (int32_t)longS.size(), pairs.data(), subst, substsz, gapo, gape, local,
+                                          res.data(), &ms, st)) != GSA_SUCCESS)
+                    return s;
+                other_ms += ms;
+                for (size_t k = 0; k < longS.size(); ++k)
+                    patch(row, longS[k], gsa::DbLanesOut {res[k].score, (int)res[k].i_end, (int)res[k].j_end, 0});
+            }
+        }
+        // results: [hits][scores][patches]
+        const size_t scoAt = ((rank ? (size_t)rows * ntop * sizeof(gsa_db_hit) : 0) + 255) & ~(size_t)255;
+        const size_t patAt = (scoAt + (scores ? (size_t)npair * 4 : 0) + 255) & ~(size_t)255;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufDbmRes], patAt + patches.size() * sizeof(gsa::DbMultiPatch), 4096)) != GSA_SUCCESS)
+            return s;
+        char* const dres = ctx->buf[kBufDbmRes].as<char>();
+        // the lane queries, longest first: the sweep classes are runs of this order
+        std::stable_sort(hq.begin(), hq.end(), [](const gsa::DbMultiQuery& x, const gsa::DbMultiQuery& y) { return x.R > y.R; });
+        auto passes_of = [](int R) { return (R + gsa::kDbLanesPassRows - 1) / gsa::kDbLanesPassRows; };
+        if (!hq.empty() &&
+            (e = hipMemcpyAsync(meta + qAt, hq.data(), hq.size() * sizeof(gsa::DbMultiQuery), hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        // the boundary rows of every class, sized before the first launch: the buffer must not move between them
+        std::vector<std::pair<size_t, size_t>> classes;  // [first, last) of hq
+        size_t bndBytes = 0;
+        std::vector<int> grids;
+        for (size_t b = 0; b < hq.size();)
+        {
+            size_t k = b;
+            const int passes = passes_of(hq[b].R);
+            while (k < hq.size() && passes_of(hq[k].R) == passes) ++k;
+            int wgs = 1;
+            if ((e = gsa::dbmulti_resident(passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            const long long nunits = (long long)(k - b) * unitsPerQuery;
+            int grid = (int)std::max<long long>(1, std::min<long long>(wgs, nunits));
+            if (max_workgroups > 0) grid = std::min(grid, max_workgroups);
+            if (passes > 1)
+                bndBytes = std::max(bndBytes, (size_t)grid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)(cmax + 1) * sizeof(int2));
+            classes.emplace_back(b, k);
+            grids.push_back(grid);
+            b = k;
+        }
+        if (bndBytes && (s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bndBytes, 4096)) != GSA_SUCCESS) return s;
+        (void)hipEventRecord(ctx->dbmev[0], st);
+        for (size_t c = 0; c < classes.size(); ++c)
+        {
+            const size_t b = classes[c].first, n = classes[c].second - b;
+            gsa::DbMultiArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.queries = queries;
+            a.q = (const gsa::DbMultiQuery*)(meta + qAt) + b;
+            a.nq = (int)n;
+            a.db = db;
+            a.subst = subst;
+            a.substsz = substsz;
+            a.go = gapo;
+            a.ge = gape;
+            a.passes = passes_of(hq[b].R);
+            a.nsubj = (int)nl;
+            a.ntasks = ntasks;
+            a.unitsPerQuery = unitsPerQuery;
+            a.nunits = (int)(n * (size_t)unitsPerQuery);
+            a.off = (const long long*)(meta + offAt);
+            a.len = (const int*)(meta + lenAt);
+            a.sidx = (const int*)(meta + idxAt);
+            a.out = dout;
+            a.ld = nsubj;
+            a.counter = (unsigned*)meta;
+            a.builds = (unsigned*)meta + 1;
+            a.bnd = a.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
+            a.bndStride = cmax + 1;
+            if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            if ((e = gsa::launch_dbmulti(a, local, grids[c], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            note_launch(ctx);
+            inf.launches += 1;
+            inf.workgroups = grids[c];
+            inf.units += a.nunits;
+            inf.lane_pairs += (int64_t)n * (int64_t)nl;
+        }
+        inf.lane_queries += (int32_t)hq.size();
+        (void)hipEventRecord(ctx->dbmev[1], st);
+        if (!patches.empty())
+        {
+            if ((e = hipMemcpyAsync(dres + patAt, patches.data(), patches.size() * sizeof(gsa::DbMultiPatch),
+                                    hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            if ((e = gsa::launch_dbmulti_scatter((const gsa::DbMultiPatch*)(dres + patAt), (long long)patches.size(), dout, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        }
+        if (scores && (e = gsa::launch_dbmulti_scores(dout, npair, (int*)(dres + scoAt), st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventRecord(ctx->dbmev[2], st);
+        if (rank && (e = gsa::launch_dbmulti_select(dout, (int)rows, nsubj, ntop, ctx->buf[kBufDbmSel].p, selTemp,
+                                                    (gsa::DbMultiHit*)dres, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventRecord(ctx->dbmev[3], st);
+        ctx->mem.glmem_peak_allocs = std::max<int64_t>(ctx->mem.glmem_peak_allocs, held_bytes(ctx));
+        if (scores && (e = hipMemcpyAsync(scores + q0 * nsubj, dres + scoAt, (size_t)npair * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        if (rank && (e = hipMemcpyAsync(hits + q0 * ntop, dres, (size_t)rows * ntop * sizeof(gsa_db_hit), hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+        (void)hipEventElapsedTime(&m0, ctx->dbmev[0], ctx->dbmev[1]);
+        (void)hipEventElapsedTime(&m1, ctx->dbmev[2], ctx->dbmev[3]);
+        (void)hipEventElapsedTime(&m2, ctx->dbmev[0], ctx->dbmev[3]);
+        lanes_ms += m0;
+        select_ms += m1;
+        all_ms += m2;
+        inf.result_bytes = std::max<int64_t>(inf.result_bytes, rows * rowBytes);
+    }
+    unsigned builds = 0;
+    if ((e = hipMemcpyAsync(&builds, meta + 4, 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    inf.profile_builds = builds;
+    inf.lanes_ms = lanes_ms;
+    inf.select_ms = select_ms;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = all_ms + other_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
+                           const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo,
+                           int32_t gape, int32_t local, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                           int32_t* scores, gsa_db_hit* hits, gsa_score_db_multi_info* info, float* kernel_ms,
+                           void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, local, top,
+                               max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int32_t gsa_score_db_multi_unit(void) { return gsa::kDbMultiUnit; }
 
 int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
                      int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,

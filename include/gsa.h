@@ -468,6 +468,57 @@ int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int
                      int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
                      char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info,
                      float* kernel_ms, void* stream);
+
+/* Many queries against one database in one call. */
+typedef struct gsa_db_hit { int32_t subject, score, i_end, j_end; } gsa_db_hit;
+
+typedef struct gsa_score_db_multi_info {  /* what the call ran; optional out-parameter */
+    int32_t lane_queries, other_queries;  /* queries on the multi-query lane kernel / sent whole through gsa_score_db_dev's path */
+    int32_t launches;                     /* lane launches (chunks x sweep classes) */
+    int32_t workgroups;                   /* grid of the last lane launch */
+    int64_t lane_pairs, units, profile_builds, result_bytes; /* result_bytes: peak device bytes of results held at once */
+    float lanes_ms, select_ms;            /* hipEvent time of the lane launches and of the ranking, summed over the chunks */
+} gsa_score_db_multi_info;
+
+/* nq queries against the nsubj subjects of a database, score-only.  db, db_off, nsubj, subst, substsz,
+ * gapo, gape, local: exactly as gsa_score_db_dev takes them.  queries and q_off follow the conventions
+ * of db and db_off: ONE device buffer holding the queries back to back, each with its header element,
+ * and a HOST table of nq + 1 strictly increasing offsets.  Synchronous.
+ * Semantics: the result of (query q, subject s) -- score and end cell, local: the first maximal cell
+ * in row-major order -- is exactly what gsa_score_db_dev returns for query q and subject s; it never
+ * depends on the path.  scores (host, int32[nq * nsubj], may be null) gets the scores, row q for query
+ * q.  hits (host, gsa_db_hit[nq * ntop], ntop = min(top, nsubj); may be null when top = 0) gets, per
+ * query, its ntop best subjects by (score descending, subject index ascending), ranked on the device.
+ * At least one of the two is non-null.
+ * All (query, subject) pairs of the subjects the lane kernel takes (1 ... Lmax letters, GSA_DB_MAXC as
+ * in gsa_score_db_dev) run in the task space of one persistent launch per sweep class (queries of
+ * 1 ... 384, 385 ... 768, ... letters) of nw_lanes_multi.hip: units of gsa_score_db_multi_unit() wave
+ * tasks of one query, query-major, longest query first, claimed by workgroups that rebuild the query
+ * profile in LDS when a unit's query is not the resident one.  max_workgroups: 0 as many workgroups as
+ * are resident, n > 0 at most n.  Pairs with an empty side are answered on the host; subjects past
+ * Lmax go through gsa_score_batch_dev's path, per query; a query whose profile does not fit LDS, one
+ * with a lane subject past the local key's bound (largest |table value| x the shorter length >= 2^18),
+ * and every query with GSA_DB_LANES=0 goes whole through gsa_score_db_dev's path.  Those results are
+ * written into the device matrix by a scatter kernel before the ranking.
+ * The results (16 bytes per pair) are held on the device for a chunk of consecutive queries at a
+ * time: scratch_limit is the bytes of result matrix held at once, 0 the default of 256 MiB; a limit
+ * below one query's row (16 nsubj bytes) is errorInvalidValue.  Each chunk is its lane launches, a
+ * ranking (top > 0; its keys take another 16 bytes per pair and the sort's own storage) and one copy
+ * back of the hits and / or score rows.  All device memory is the context's and counted in
+ * gsa_mem_stats.
+ * Everything gsa_score_db_dev rejects, for either offset table, nq < 1, a negative top, max_workgroups
+ * or scratch_limit, scores and hits both null, or hits null with top > 0 and scores null, is
+ * errorInvalidValue before anything is enqueued.  The call adds no launch kind and no knob: the record
+ * of gsa_last_launch is left untouched and *info (may be null) says what ran; the fills' sticky error
+ * word is left alone.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call. */
+int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                           const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                           const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                           int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                           int32_t* scores, gsa_db_hit* hits,
+                           gsa_score_db_multi_info* info, float* kernel_ms, void* stream);
+/* Wave tasks (of four subjects) in a unit of gsa_score_db_multi_dev: a compile-time constant. */
+int32_t gsa_score_db_multi_unit(void);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
