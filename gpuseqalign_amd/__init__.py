@@ -147,6 +147,14 @@ class ScoreDbMultiInfo(ctypes.Structure):
                 ("select_ms", ctypes.c_float)]
 
 
+class AlignDbMultiInfo(ctypes.Structure):
+    """gsa_align_db_multi_info (include/gsa.h): what the last gsa_align_db_multi_dev call ran."""
+    _fields_ = [("lane_hits", ctypes.c_int32), ("unsupported", ctypes.c_int32), ("chunks", ctypes.c_int32),
+                ("launches", ctypes.c_int32), ("workgroups", ctypes.c_int32), ("lane_queries", ctypes.c_int32),
+                ("tasks", ctypes.c_int64), ("units", ctypes.c_int64), ("profile_builds", ctypes.c_int64),
+                ("code_bytes", ctypes.c_int64), ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float)]
+
+
 # numpy view of DbHit: the records of Engine.score_db_multi_dev's "hits"
 DB_HIT_DTYPE = np.dtype([("subject", np.int32), ("score", np.int32), ("i_end", np.int32), ("j_end", np.int32)])
 
@@ -225,6 +233,11 @@ SIGNATURES = {
                                               ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
                                               ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_multi_unit": (_i32, []),
+    "gsa_align_db_multi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32, _i32p,
+                                              _i32p, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i64,
+                                              ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                              ctypes.POINTER(AlignDbMultiInfo), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_db_multi_unit": (_i32, []),
     "gsa_score":(ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -272,6 +285,11 @@ def _c32(a) -> np.ndarray:
 def score_db_multi_unit() -> int:
     """Wave tasks (of four subjects) in a unit of gsa_score_db_multi_dev."""
     return int(lib().gsa_score_db_multi_unit())
+
+
+def align_db_multi_unit() -> int:
+    """Wave tasks (of up to four hits) in a unit of gsa_align_db_multi_dev."""
+    return int(lib().gsa_align_db_multi_unit())
 
 
 def sparse_tile_by() -> int:
@@ -725,6 +743,67 @@ class Engine:
                        top: int = 0) -> dict:
         """score_db_multi_dev over host arrays: every entry of `queries` and of `subjects` with the
         header element in front, as score_db takes them."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.score_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
+                                       local, top)
+
+    # -- the alignments of many queries' hits in one call (DESIGN.md 2.2g) -------------------
+
+    def align_db_multi_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, hit_query, hit_subject, subst_ptr: int,
+                           substsz: int, gapo: int, gape: Optional[int] = None, local: bool = False,
+                           max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None) -> list:
+        """The alignments of chosen (query, subject) pairs (gsa_align_db_multi_dev; synchronous):
+        queries, database and table as score_db_multi_dev takes them, `hit_query` and `hit_subject`
+        the pairs' indices (any order, repeats allowed).  One dict per pair, in order, equal to
+        align_db_dev's for that query and subject: {"score", "status", "i_start", "j_start", "i_end",
+        "j_end", "cigar", "kernel_ms"}.  `max_workgroups` caps the fill's grid (0: all resident),
+        `scratch_limit` the bytes of move codes held at once (0: the default).
+        last_align_db_multi_info() says what the call ran."""
+        qo = np.ascontiguousarray(q_off, dtype=np.int64)
+        off = np.ascontiguousarray(db_off, dtype=np.int64)
+        hq = np.ascontiguousarray(hit_query, dtype=np.int32).ravel()
+        hs = np.ascontiguousarray(hit_subject, dtype=np.int32).ravel()
+        if len(hq) != len(hs):
+            raise NwError(NwStat.errorInvalidValue, "align_db_multi_dev: hit_query and hit_subject differ in length")
+        nq, n, nh = len(qo) - 1, len(off) - 1, len(hq)
+        res = (AlignDbResult * max(nh, 1))()
+        info = AlignDbMultiInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes per hit always suffice
+        cap = 0
+        if nh and n >= 1 and nq >= 1 and hs.min() >= 0 and hs.max() < n and hq.min() >= 0 and hq.max() < nq:
+            cap = int(2 * (np.diff(off)[hs].clip(1) - 1 + np.diff(qo)[hq].clip(1) - 1).sum() + nh)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        i64p = ctypes.POINTER(_i64)
+        st = lib().gsa_align_db_multi_dev(
+            self._h, queries_ptr, qo.ctypes.data_as(i64p), nq, db_ptr, off.ctypes.data_as(i64p), n,
+            hq.ctypes.data_as(_i32p), hs.ctypes.data_as(_i32p), nh, subst_ptr, substsz, gapo,
+            gapo if gape is None else gape, int(local), int(max_workgroups), int(scratch_limit), res, buf, cap,
+            ctypes.byref(need), ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_db_multi_dev")
+        self._align_db_multi_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                     for k, t in info._fields_}
+        raw = buf.raw
+        out = []
+        for r in res[:nh]:
+            cig = raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else ""
+            out.append({"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start),
+                        "j_start": int(r.j_start), "i_end": int(r.i_end), "j_end": int(r.j_end), "cigar": cig,
+                        "kernel_ms": float(ms.value)})
+        return out
+
+    def last_align_db_multi_info(self) -> dict:
+        """gsa_align_db_multi_info of the last align_db_multi_dev call on this engine: "lane_hits",
+        "unsupported", "chunks", "launches", "workgroups", "lane_queries", "tasks", "units",
+        "profile_builds", "code_bytes", "fill_ms", "walk_ms"."""
+        info = getattr(self, "_align_db_multi_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_db_multi_info: no align_db_multi_dev call yet")
+        return dict(info)
+
+    def _pack_db_multi(self, queries, subjects, subst):
+        """Queries, subjects and table on the device, uploaded once: (dQ, qoff, dD, off, dS, substsz)."""
         import torch
         dev = torch.device("cuda", self.device)
         up = lambda a: torch.from_numpy(_c32(a)).to(dev)
@@ -741,22 +820,33 @@ class Engine:
         dS = up(subst.ravel())
         (dQ, qoff), (dD, off) = pack(queries), pack(subjects)
         torch.cuda.synchronize(dev)
-        return self.score_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
-                                       local, top)
+        return dQ, qoff, dD, off, dS, substsz
+
+    def align_db_multi(self, queries, subjects, hit_query, hit_subject, subst, gapo: int, gape: Optional[int] = None,
+                       local: bool = False) -> list:
+        """align_db_multi_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front; `hit_query` indexes `queries`, `hit_subject` indexes `subjects`."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.align_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hit_query, hit_subject, dS.data_ptr(),
+                                       substsz, gapo, gape, local)
 
     def search_db_multi(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
                         top: int = 10) -> list:
-        """Database search with alignments for many queries: one score_db_multi with `top`, then
-        align_db per query on its hits.  Per query [(subject_index, result dict)], equal to
-        [search_db(q, ...) for q in queries]."""
+        """Database search with alignments for many queries: queries, subjects and table are uploaded
+        once, then one score_db_multi_dev with `top` and one align_db_multi_dev on all the hits.  Per
+        query [(subject_index, result dict)], equal to [search_db(q, ...) for q in queries]."""
         if max(int(top), 0) == 0:
             return [[] for _ in queries]
-        hits = self.score_db_multi(queries, subjects, subst, gapo, gape, local, top)["hits"]
-        out = []
-        for q, row in zip(queries, hits):
-            order = [int(s) for s in row["subject"]]
-            out.append(list(zip(order, self.align_db(q, subjects, order, subst, gapo, gape, local))) if order else [])
-        return out
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        hits = self.score_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape,
+                                       local, top, want_scores=False)["hits"]
+        hq = np.repeat(np.arange(hits.shape[0], dtype=np.int32), hits.shape[1])
+        hs = np.ascontiguousarray(hits["subject"], dtype=np.int32).ravel()
+        res = self.align_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hq, hs, dS.data_ptr(), substsz, gapo,
+                                      gape, local)
+        ntop = hits.shape[1]
+        return [list(zip([int(x) for x in hs[q * ntop:(q + 1) * ntop]], res[q * ntop:(q + 1) * ntop]))
+                for q in range(hits.shape[0])]
 
     # -- device-side verification (SURVEY.md 8(f)1) ---------------------------------------
 

@@ -1,8 +1,8 @@
 // gsa_score.hip -- the score-only and database entry points of libgsa.so (declared in include/gsa.h):
-// gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev, gsa_score_db_multi_dev and
-// gsa_align_db_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
+// gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev, gsa_score_db_multi_dev,
+// gsa_align_db_dev and gsa_align_db_multi_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
 // (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
-// nw_lanes_multi.hip, nw_lanes_trace.hip).  The context
+// nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip).  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,7 @@
 #include "nw_lanes.h"
 #include "nw_lanes_multi.h"
 #include "nw_lanes_trace.h"
+#include "nw_lanes_trace_multi.h"
 #include "nw_scan.h"
 #include "nw_strip.h"
 
@@ -1559,9 +1560,323 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
     return GSA_SUCCESS;
 }
 
+
+// gsa_align_db_multi_dev: the hits of many queries in one call.  Every pair is routed as
+// align_db_impl routes it for that query (empty sides on the host, status 1 through one
+// score_batch_impl call for all queries); the traced hits follow the plan of
+// nw_lanes_trace_multi_plan.h: per chunk one upload of its records, one fill launch per sweep class
+// (nw_lanes_trace_multi.hip), one walk launch over all its hits and one copy back.  The code, meta and
+// result buffers are gsa_align_db_dev's.  gsa_last_launch's record is left as it was.
+int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
+                        const int64_t* db_off, int32_t nsubj, const int32_t* hit_query, const int32_t* hit_subject,
+                        int32_t nhits, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                        int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                        int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_multi_info* info, float* kernel_ms,
+                        hipStream_t st)
+{
+    if (!ctx || !queries || !q_off || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    if (nq < 1 || nsubj < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (nhits < 0 || max_workgroups < 0 || scratch_limit < 0 || cigar_cap < 0) return GSA_ERROR_INVALID_VALUE;
+    if ((nhits > 0 && (!hit_query || !hit_subject)) || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (!offsets_ok(q_off, nq) || !offsets_ok(db_off, nsubj)) return GSA_ERROR_INVALID_VALUE;
+    for (int h = 0; h < nhits; ++h)
+        if (hit_query[h] < 0 || hit_query[h] >= nq || hit_subject[h] < 0 || hit_subject[h] >= nsubj)
+            return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_db_multi_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    auto rows_of = [&](int q) { return q_off[q + 1] - q_off[q] - 1; };
+    auto cols_of = [&](int s) { return db_off[s + 1] - db_off[s] - 1; };
+    int64_t Rmax = 0, Cmax = 0;
+    for (int q = 0; q < nq; ++q) Rmax = std::max(Rmax, rows_of(q));
+    for (int s = 0; s < nsubj; ++s) Cmax = std::max(Cmax, cols_of(s));
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    long long smax = 1;
+    if (Rmax > 0 && Cmax > 0)
+    {
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        smax = subst_absmax(sub.data(), substsz);
+        // score_ranges' bounds grow with R and with C: the longest query against the longest subject
+        // is outside every kernel's range iff any pair is
+        bool stripOk = false;
+        const int s = score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
+        if (s != GSA_SUCCESS) return s;
+    }
+    if (nhits == 0) return GSA_SUCCESS;
+    const KeepLaunchRecord keep(ctx);
+
+    // the route of every pair, with that hit's query: align_db_impl's conditions
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : kAlignDbScratch;
+    std::vector<std::string> cig((size_t)nhits);
+    std::vector<unsigned char> lane((size_t)nhits, 0);
+    std::vector<int> other;
+    for (int h = 0; h < nhits; ++h)
+    {
+        const int64_t R = rows_of(hit_query[h]), C = cols_of(hit_subject[h]);
+        gsa_align_db_result& r = out[h];
+        std::memset(&r, 0, sizeof(r));
+        if (R == 0 || C == 0)
+        {
+            const int64_t k = R + C;
+            if (!local && k > 0)
+            {
+                r.score = (int32_t)(gapo + (k - 1) * gape);
+                r.i_end = R;
+                r.j_end = C;
+                cig[(size_t)h] = std::to_string(k) + (R > 0 ? 'I' : 'D');
+            }
+            continue;
+        }
+        const bool fits = R < (1 << 20) && gsa::dblanes_lds_bytes((int)R, substsz) <= (size_t)ctx->lds_max;
+        const bool keyOk = !local || smax * std::min(R, C) < gsa::kDbLanesMaxScore;
+        const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+        const bool take = fits && C <= gsa::kDbLanesMaxC && keyOk && valOk && gsa::dbtrace_code_bytes(R, C) <= limit;
+        if (take)
+            lane[(size_t)h] = 1;
+        else
+            other.push_back(h);
+    }
+    float fill_ms = 0.f, walk_ms = 0.f, other_ms = 0.f;
+    const std::vector<gsa::DbaChunk> plan =
+        gsa::dba_plan(nhits, hit_query, hit_subject, q_off, db_off, lane.data(), limit, gsa::kDbAlignMultiUnit);
+    if (!plan.empty())
+    {
+        static_assert(sizeof(gsa::DbaQuery) == 16 && sizeof(gsa::DbaTask) == 8 && sizeof(gsa::DbaUnit) == 16, "device records");
+        // the largest of every buffer over the chunks, and every launch's grid
+        size_t maxN = 0, maxQ = 0, maxT = 0, maxU = 0, bndBytes = 0;
+        int64_t maxCodes = 0, maxMoves = 0;
+        std::vector<std::vector<int>> grids(plan.size());
+        for (size_t c = 0; c < plan.size(); ++c)
+        {
+            const gsa::DbaChunk& ch = plan[c];
+            maxN = std::max(maxN, ch.hits.size());
+            maxQ = std::max(maxQ, ch.queries.size());
+            maxT = std::max(maxT, ch.tasks.size());
+            maxU = std::max(maxU, ch.units.size());
+            maxCodes = std::max<int64_t>(maxCodes, ch.codeBytes);
+            maxMoves = std::max<int64_t>(maxMoves, ch.moveBytes);
+            for (const gsa::DbaLaunch& L : ch.launches)
+            {
+                int wgs = 1;
+                if ((e = gsa::dbtrace_multi_resident(L.passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                int grid = std::max(1, std::min(wgs, L.nunits));
+                if (max_workgroups > 0) grid = std::min(grid, max_workgroups);
+                grids[c].push_back(grid);
+                if (L.passes > 1)
+                    bndBytes = std::max(bndBytes, (size_t)grid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)(ch.cmax + 1) * sizeof(int2));
+            }
+        }
+        // meta: [unit counter, profile builds; 64 B][offsets][query offsets][code offsets][move offsets]
+        //       [lengths][queries][tasks][units][fill results]
+        auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+        const size_t offAt = 64, qoffAt = offAt + maxN * 8, coffAt = qoffAt + maxN * 8, moffAt = coffAt + maxN * 8;
+        const size_t lenAt = moffAt + maxN * 8, qAt = up16(lenAt + maxN * 4), taskAt = qAt + maxQ * sizeof(gsa::DbaQuery);
+        const size_t unitAt = up16(taskAt + maxT * sizeof(gsa::DbaTask)), foutAt = unitAt + maxU * sizeof(gsa::DbaUnit);
+        const size_t metaBytes = foutAt + maxN * sizeof(gsa::DbLanesOut);
+        // results: [walk results][move bytes]
+        const size_t movAt = maxN * sizeof(gsa::DbTraceOut);
+        const size_t resBytes = movAt + (size_t)maxMoves;
+        int s;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufAdbMeta], metaBytes, 4096)) != GSA_SUCCESS ||
+            (s = reserve_hard(ctx, ctx->buf[kBufAdbRes], resBytes, 4096)) != GSA_SUCCESS ||
+            (s = reserve_hard(ctx, ctx->buf[kBufAdbCodes], (size_t)maxCodes, 4096)) != GSA_SUCCESS)
+            return s;
+        if (bndBytes && (s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bndBytes, 4096)) != GSA_SUCCESS) return s;
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        char* const meta = ctx->buf[kBufAdbMeta].as<char>();
+        unsigned char* const adbres = ctx->buf[kBufAdbRes].as<unsigned char>();
+        if ((e = hipMemsetAsync(meta, 0, 64, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        std::vector<char> hmeta(foutAt), hres(resBytes);
+        for (size_t c = 0; c < plan.size(); ++c)
+        {
+            const gsa::DbaChunk& ch = plan[c];
+            const size_t n = ch.hits.size();
+            long long* const hoff = (long long*)(hmeta.data() + offAt);
+            long long* const hqoff = (long long*)(hmeta.data() + qoffAt);
+            long long* const hcoff = (long long*)(hmeta.data() + coffAt);
+            long long* const hmoff = (long long*)(hmeta.data() + moffAt);
+            int* const hlen = (int*)(hmeta.data() + lenAt);
+            for (size_t k = 0; k < n; ++k)
+            {
+                hoff[k] = ch.hits[k].dbOff;
+                hqoff[k] = ch.hits[k].qOff;
+                hcoff[k] = ch.hits[k].codeOff;
+                hmoff[k] = ch.hits[k].moveOff;
+                hlen[k] = ch.hits[k].C;
+            }
+            std::memcpy(hmeta.data() + qAt, ch.queries.data(), ch.queries.size() * sizeof(gsa::DbaQuery));
+            std::memcpy(hmeta.data() + taskAt, ch.tasks.data(), ch.tasks.size() * sizeof(gsa::DbaTask));
+            std::memcpy(hmeta.data() + unitAt, ch.units.data(), ch.units.size() * sizeof(gsa::DbaUnit));
+            if ((e = hipMemcpyAsync(meta + offAt, hmeta.data() + offAt, foutAt - offAt, hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            (void)hipEventRecord(ctx->adbev[0], st);
+            for (size_t l = 0; l < ch.launches.size(); ++l)
+            {
+                const gsa::DbaLaunch& L = ch.launches[l];
+                gsa::DbTraceMultiArgs a;
+                std::memset(&a, 0, sizeof(a));
+                a.queries = queries;
+                a.db = db;
+                a.subst = subst;
+                a.substsz = substsz;
+                a.go = gapo;
+                a.ge = gape;
+                a.passes = L.passes;
+                a.q = (const gsa::DbaQuery*)(meta + qAt);
+                a.units = (const gsa::DbaUnit*)(meta + unitAt) + L.firstUnit;
+                a.nunits = L.nunits;
+                a.tasks = (const gsa::DbaTask*)(meta + taskAt);
+                a.off = (const long long*)(meta + offAt);
+                a.len = (const int*)(meta + lenAt);
+                a.codeOff = (const long long*)(meta + coffAt);
+                a.out = (gsa::DbLanesOut*)(meta + foutAt);
+                a.codes = ctx->buf[kBufAdbCodes].as<unsigned char>();
+                a.counter = (unsigned*)meta;
+                a.builds = (unsigned*)meta + 1;
+                a.bnd = L.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
+                a.bndStride = ch.cmax + 1;
+                if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                if ((e = gsa::launch_dbtrace_multi_fill(a, local, grids[c][l], st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                note_launch(ctx);
+                inf.launches += 1;
+                inf.workgroups = grids[c][l];
+            }
+            (void)hipEventRecord(ctx->adbev[1], st);
+            gsa::DbTraceMultiWalkArgs w;
+            std::memset(&w, 0, sizeof(w));
+            w.queries = queries;
+            w.db = db;
+            w.nhits = (int)n;
+            w.local = local;
+            w.qoff = (const long long*)(meta + qoffAt);
+            w.off = (const long long*)(meta + offAt);
+            w.len = (const int*)(meta + lenAt);
+            w.out = (const gsa::DbLanesOut*)(meta + foutAt);
+            w.codes = ctx->buf[kBufAdbCodes].as<unsigned char>();
+            w.codeOff = (const long long*)(meta + coffAt);
+            w.moveOff = (const long long*)(meta + moffAt);
+            w.res = (gsa::DbTraceOut*)adbres;
+            w.moves = adbres + movAt;
+            if ((e = gsa::launch_dbtrace_multi_walk(w, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            (void)hipEventRecord(ctx->adbev[2], st);
+            if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)ch.moveBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            float m0 = 0.f, m1 = 0.f;
+            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+            fill_ms += m0;
+            walk_ms += m1;
+            const gsa::DbTraceOut* const ho = (const gsa::DbTraceOut*)hres.data();
+            for (size_t k = 0; k < n; ++k)
+            {
+                const gsa::DbaHit& H = ch.hits[k];
+                gsa_align_db_result& r = out[H.hit];
+                r.score = ho[k].score;
+                r.i_start = ho[k].i_start;
+                r.j_start = ho[k].j_start;
+                r.i_end = ho[k].i_end;
+                r.j_end = ho[k].j_end;
+                if (ho[k].moves < 0 || ho[k].moves > H.moveLen) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                cig[(size_t)H.hit] = fold_cigar((const unsigned char*)hres.data() + movAt + H.moveOff, ho[k].moves);
+            }
+            inf.chunks += 1;
+            inf.lane_hits += (int32_t)n;
+            inf.lane_queries += (int32_t)ch.queries.size();
+            inf.tasks += (int64_t)ch.tasks.size();
+            inf.units += (int64_t)ch.units.size();
+            inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
+        }
+        unsigned builds = 0;
+        if ((e = hipMemcpyAsync(&builds, meta + 4, 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        inf.profile_builds = builds;
+    }
+    if (!other.empty())
+    {
+        // score and end cell from the score path, all queries' pairs in one batch
+        std::vector<gsa_pair_dev> pairs(other.size());
+        std::vector<gsa_score_result> res(other.size());
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            const int h = other[k];
+            gsa_pair_dev& p = pairs[k];
+            std::memset(&p, 0, sizeof(p));
+            p.seqY = queries + q_off[hit_query[h]];
+            p.adjrows = (int32_t)(rows_of(hit_query[h]) + 1);
+            p.seqX = db + db_off[hit_subject[h]];
+            p.adjcols = (int32_t)(cols_of(hit_subject[h]) + 1);
+        }
+        const int s = score_batch_impl(ctx, (int32_t)other.size(), pairs.data(), subst, substsz, gapo, gape, local,
+                                       res.data(), &other_ms, st);
+        if (s != GSA_SUCCESS) return s;
+        for (size_t k = 0; k < other.size(); ++k)
+        {
+            gsa_align_db_result& r = out[other[k]];
+            r.score = res[k].score;
+            r.i_end = res[k].i_end;
+            r.j_end = res[k].j_end;
+            r.status = 1;
+        }
+        inf.unsupported = (int32_t)other.size();
+    }
+    // the strings back to back in hit order; a hit's offset does not depend on the buffer's size
+    int64_t at = 0;
+    for (int h = 0; h < nhits; ++h)
+    {
+        gsa_align_db_result& r = out[h];
+        const int64_t len = (int64_t)cig[(size_t)h].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)h].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+    }
+    if (cigar_need) *cigar_need = at;
+    inf.fill_ms = fill_ms;
+    inf.walk_ms = walk_ms;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = fill_ms + walk_ms + other_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
+                           const int64_t* db_off, int32_t nsubj, const int32_t* hit_query, const int32_t* hit_subject,
+                           int32_t nhits, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                           int32_t local, int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
+                           char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_multi_info* info,
+                           float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
+                               gapo, gape, local, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need, info,
+                               kernel_ms, pick_stream(ctx, stream));
+}
+
+int32_t gsa_align_db_multi_unit(void) { return gsa::kDbAlignMultiUnit; }
 
 int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                            const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo,

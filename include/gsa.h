@@ -519,6 +519,55 @@ int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
                            gsa_score_db_multi_info* info, float* kernel_ms, void* stream);
 /* Wave tasks (of four subjects) in a unit of gsa_score_db_multi_dev: a compile-time constant. */
 int32_t gsa_score_db_multi_unit(void);
+
+/* The alignments of many queries' hits in one call. */
+typedef struct gsa_align_db_multi_info {  /* what the call ran; optional out-parameter */
+    int32_t lane_hits;      /* hits traced on the device */
+    int32_t unsupported;    /* hits with status 1 */
+    int32_t chunks;         /* chunks: one walk launch and one copy back each */
+    int32_t launches;       /* fill launches (chunks x sweep classes) */
+    int32_t workgroups;     /* grid of the last fill launch */
+    int32_t lane_queries;   /* queries with traced hits, summed over the chunks */
+    int64_t tasks, units;   /* wave tasks and units over all chunks */
+    int64_t profile_builds; /* query profiles built in LDS, over all launches */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    float fill_ms, walk_ms; /* hipEvent time of the fill and of the walk launches, summed over the chunks */
+} gsa_align_db_multi_info;
+
+/* The alignments of nhits (query, subject) pairs, traced on the device.  queries, q_off, nq, db, db_off,
+ * nsubj, subst, substsz, gapo, gape, local: exactly as gsa_score_db_multi_dev takes them.  hit_query and
+ * hit_subject are HOST arrays of nhits indices (0 ... nq - 1 and 0 ... nsubj - 1), in any order; a pair
+ * may be named twice.  out is a host array of nhits results.  Synchronous.
+ * Semantics: out[h] is, field for field, what gsa_align_db_dev returns for query hit_query[h] and the
+ * single hit hit_subject[h] under the same scratch_limit: score, status, both cells and the CIGAR.
+ * The status 1 conditions of gsa_align_db_dev are evaluated per pair with that hit's query, and the
+ * status 1 hits of all queries take one gsa_score_batch_dev pass; pairs with an empty side are answered
+ * on the host.  The CIGAR buffer follows gsa_align_db_dev's rules: strings back to back in hit order,
+ * NUL-terminated, offsets independent of cigar_cap, status 2 for a string that does not fit,
+ * *cigar_need the bytes all of them need.
+ * The traced hits are ordered by query length (longest first), query, and subject length (longest
+ * first), and cut greedily into chunks whose move codes fit scratch_limit (0: 256 MiB).  In a chunk the
+ * hits of one query form wave tasks of up to four hits and units of up to gsa_align_db_multi_unit()
+ * consecutive tasks; the units of one sweep class (queries of 1 ... 384, 385 ... 768, ... letters) are
+ * one persistent fill launch of nw_lanes_trace_multi.hip, whose workgroups claim units and rebuild the
+ * query profile in LDS when a unit's query is not the resident one; one walk launch and one copy back
+ * serve the whole chunk.  max_workgroups: 0 as many workgroups as are resident, n > 0 at most n.  The
+ * scratch is gsa_align_db_dev's and counted in gsa_mem_stats.
+ * Everything gsa_align_db_dev rejects, for either offset table, nq < 1, a hit index out of range, a null
+ * hit_query or hit_subject with nhits > 0, a negative nhits, max_workgroups, scratch_limit or cigar_cap,
+ * or the longest query against the longest subject outside every kernel's value range is
+ * errorInvalidValue before anything is enqueued; nhits = 0 succeeds with nothing launched.  The call
+ * adds no launch kind and no knob: the record of gsa_last_launch is left untouched and *info (may be
+ * null) says what ran.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call. */
+int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                           const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                           const int32_t* hit_query, const int32_t* hit_subject, int32_t nhits,
+                           const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                           int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
+                           char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                           gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
+/* Wave tasks (of up to four hits) in a unit of gsa_align_db_multi_dev: a compile-time constant. */
+int32_t gsa_align_db_multi_unit(void);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
