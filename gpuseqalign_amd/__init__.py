@@ -262,6 +262,13 @@ def lib():
     if _LIB is None:
         if not os.path.exists(_SO):
             raise ImportError(f"{_SO} missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)")
+        # PyTorch-ROCm may ship a HIP runtime of its own.  Loaded after libgsa.so it is a second runtime
+        # in the process, and whichever of the two initialises second finds no device; loaded first, it
+        # has the name libgsa.so asks for and serves both.
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
         L = ctypes.CDLL(_SO)
         for name, (res, args) in SIGNATURES.items():
             if os.environ.get("GSA_LIB") and not hasattr(L, name):

@@ -425,8 +425,11 @@ int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* 
     const unsigned err = (unsigned)res[3];
     (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
     out->calc_kernel_ms += bidiMs;  // (a local pair back from both ends: both launches)
-    // a substitution value outside int16 after the shift: the int32 row scan computes it
-    if (err == 2u) return kScoreTooLarge;
+    // a substitution value outside int16 after the shift: the int32 row scan computes it.  Bit 2 alone
+    // from the K-rows kernel (every workgroup checks the whole table and claims no ticket); the strip
+    // kernel's waves check the table rows of their own letters, and a wave that meets the raised flag
+    // in a wait gives up with bit 1 as well: with bit 2 set that is no failure of its own
+    if (err & 2u) return kScoreTooLarge;
     if (err != 0) return GSA_ERROR_KERNEL_FAILURE;
     if (local)
     {
@@ -465,9 +468,23 @@ long long subst_absmax(const int32_t* sub, int32_t substsz)
 int score_ranges(int64_t R, int64_t C, long long smax, int32_t gapo, int32_t gape, int32_t local, bool* stripOk)
 {
     const long long span = (R + C) * (long long)(-gape) + (long long)(gape - gapo) + smax;
-    // unshifted int32 (row scan): |H| <= smax*min(R,C) + |go| + (R+C)|ge|
-    if (smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= (1ll << 30))
-        return GSA_ERROR_INVALID_VALUE;
+    // unshifted int32 (row scan, lane kernels): |H| <= B = smax*min(R,C) + |go| + (R+C)|ge|, by the path
+    // of min(i,j) diagonal steps and one gap; every sum of two values then stays inside int32
+    const long long B = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape);
+    if (B >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+    // Global modes: the kernels stand in for minus infinity with NEG = -2^29 (E left of column 1, F
+    // above row 1, the cells before the matrix), and E = max(E_left + ge, H_left + go) is right only
+    // while the true term wins: a value that comes from NEG is at most NEG + ge, a true H + go at
+    // least -B + go, so -B - |go| >= -2^29 - |ge| is needed.  Once the first E of a row (F of a column)
+    // is the true one, every later one is a maximum over true terms and one term <= NEG + ge, by
+    // induction.  Shipped without the |ge| of slack: B + |go| < 2^29.  It holds for the shifted kernels
+    // as well (their H' = H - (i+j) ge >= H >= -B, their NEG is the same).  Past it no kernel runs: at
+    // -2000010 / -2000000 the same recurrence on the CPU scores a 300 x 10 pair -538870873 where
+    // -579999935 is right (tests/test_exact_reference.py).
+    // Local modes are left at B < 2^30: H >= 0 there, a value from NEG is negative wherever it stands
+    // (NEG + (R+C) ge > -2^31), so it can only replace a true E or F that is negative too, and both
+    // lose against the clamp (tests/test_gpu_value_ranges.py runs them at the same gap costs).
+    if (!local && B + (long long)(-gapo) >= (1ll << 29)) return GSA_ERROR_INVALID_VALUE;
     const int bits = sw_idx_bits(R, C);
     const long long scoreBound = std::min<long long>((1ll << 31) - 1, smax * std::min(R, C));
     const int scoreBits = scoreBound > 0 ? 64 - __builtin_clzll((unsigned long long)scoreBound) : 1;

@@ -341,7 +341,16 @@ int gsa_trace_sparse_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, con
  *   H = max(H_diag + s, E, F [, 0 if local]); a gap of length L costs gapo + (L-1)*gape;
  *   global: score = H[R][C], boundaries gapo + (k-1)*gape; local: max over H, end = first
  *   cell in row-major order.  gapo == gape == g is the reference's NW-LG.  Requires
- *   gapo <= gape <= 0.  Synchronous. */
+ *   gapo <= gape <= 0.  Synchronous.
+ * Accepted value range, the same for all six device entry points below and for gsa_score: with
+ * smax the largest |table value| (at least 1), R and C the letter counts and
+ *   B = smax min(R, C) + |gapo| + (R + C) |gape|      (no |H| exceeds it)
+ * a global pair needs B + |gapo| < 2^29 and a local pair B < 2^30; a local pair also needs
+ * ceil(log2((R + 1)(C + 1))) + bits(min(smax min(R, C), 2^31 - 1)) <= 63 for its end-cell key.
+ * A pair outside is errorInvalidValue before anything is enqueued; every pair inside is computed
+ * exactly, on whichever kernel takes it ("Value-range guards").  The kernels keep
+ * -2^29 for minus infinity: the global bound is what keeps every true H + gapo above it; local
+ * values never fall below 0, so nothing that comes from it can win there. */
 /* gsa_score_dev reads the substitution table back in stream order (it sizes the value range
  * from it) before its launch; the score kernels report errors in a control word of their own, so
  * the fills' sticky error word is left for the caller's gsa_sync.  Global scores of long pairs run
@@ -358,6 +367,7 @@ typedef struct gsa_score_result
                             * ends) the prep, fill and combine kernels, and a local
                             * pair's second launch when it needed one */
 } gsa_score_result;
+/* Accepted range: global B + |gapo| < 2^29, local B < 2^30 (above); else errorInvalidValue. */
 int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
                   gsa_score_result* out, void* stream);
@@ -382,7 +392,9 @@ int gsa_score_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int3
  * control word, as gsa_score_dev's.  gsa_last_launch then reports the batch launch (kind
  * GSA_LAUNCH_SCORE_KROW, npairs as passed, the tickets of all pairs, k, q8, pair_major), or the
  * last single-pair launch when a pair took the fallback.
- * Pairs much shorter than a ticket leave most of its lanes idle. */
+ * Pairs much shorter than a ticket leave most of its lanes idle.
+ * Accepted range: gsa_score_dev's, for every pair (global B + |gapo| < 2^29, local B < 2^30); one
+ * pair outside it makes the call errorInvalidValue before anything is enqueued. */
 int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
                         int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
                         float* batch_kernel_ms, void* stream);
@@ -404,7 +416,9 @@ int gsa_score_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs,
  * gapo > gape, gape > 0, substsz outside 1..32 or a pair outside every kernel's value range is
  * errorInvalidValue before anything is enqueued.  The fills' sticky error word is left alone.
  * gsa_last_launch reports the lane launch (kind GSA_LAUNCH_SCORE_LANES) when any subject took it,
- * else what the other path reports. */
+ * else what the other path reports.
+ * Accepted range: gsa_score_dev's, for the query against every subject with letters (global
+ * B + |gapo| < 2^29, local B < 2^30). */
 int gsa_score_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db,
                      const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz,
                      int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out,
@@ -462,7 +476,10 @@ typedef struct gsa_align_db_info {  /* what the call ran; optional out-parameter
  * context is errorInvalidValue before anything is enqueued; nhits = 0 succeeds with nothing launched.
  * *info (may be null) says what the call ran.  This call adds no launch kind and no knob: the record
  * of gsa_last_launch is left untouched, also by the status 1 hits' score launches.  *kernel_ms (may be
- * null) gets the hipEvent time of all kernels of the call. */
+ * null) gets the hipEvent time of all kernels of the call.
+ * Accepted range: gsa_score_db_dev's, over the whole database and not the hits alone (global
+ * B + |gapo| < 2^29, local B < 2^30).  The trace fills keep -2^27 for minus infinity, which the
+ * status 1 bound B < 2^26 keeps below every true H + gapo. */
 int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_t* db, const int64_t* db_off,
                      int32_t nsubj, const int32_t* hits, int32_t nhits, const int32_t* subst, int32_t substsz,
                      int32_t gapo, int32_t gape, int32_t local, int64_t scratch_limit, gsa_align_db_result* out,
@@ -510,7 +527,9 @@ typedef struct gsa_score_db_multi_info {  /* what the call ran; optional out-par
  * or scratch_limit, scores and hits both null, or hits null with top > 0 and scores null, is
  * errorInvalidValue before anything is enqueued.  The call adds no launch kind and no knob: the record
  * of gsa_last_launch is left untouched and *info (may be null) says what ran; the fills' sticky error
- * word is left alone.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call. */
+ * word is left alone.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call.
+ * Accepted range: gsa_score_dev's for the longest query against the longest subject (global
+ * B + |gapo| < 2^29, local B < 2^30), which bounds every pair's. */
 int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
                            const int32_t* db, const int64_t* db_off, int32_t nsubj,
                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
@@ -558,7 +577,9 @@ typedef struct gsa_align_db_multi_info {  /* what the call ran; optional out-par
  * or the longest query against the longest subject outside every kernel's value range is
  * errorInvalidValue before anything is enqueued; nhits = 0 succeeds with nothing launched.  The call
  * adds no launch kind and no knob: the record of gsa_last_launch is left untouched and *info (may be
- * null) says what ran.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call. */
+ * null) says what ran.  *kernel_ms (may be null) gets the hipEvent time of all kernels of the call.
+ * Accepted range: gsa_score_db_multi_dev's (the longest query against the longest subject: global
+ * B + |gapo| < 2^29, local B < 2^30). */
 int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
                            const int32_t* db, const int64_t* db_off, int32_t nsubj,
                            const int32_t* hit_query, const int32_t* hit_subject, int32_t nhits,

@@ -24,6 +24,12 @@
  *   local:  H[0][j] = H[i][0] = 0, E/F on the boundary = NEG;  score = max over all H (the
  *           boundary zeros included), end = the first (i, j) in row-major order holding it.
  * Sequences carry the dummy element 0 (src/file_formats.cpp:43-47): adjrows = R+1.
+ *
+ * Valid range.  NEG is finite, so a global result is right only while every true H + go stays above
+ * NEG + ge: with B = max|s| min(R, C) + |go| + (R + C) |ge| bounding |H|, B + |go| < 2^29 suffices, and
+ * that is the range the library accepts (gsa_score.hip score_ranges).  Local results are right up to
+ * B < 2^30 (H >= 0: nothing that comes from NEG ever wins).  tests/test_exact_reference.py holds this
+ * file against an int64 restatement with a true minus infinity on both sides of that line.
  */
 #include <stdint.h>
 #include <stdlib.h>

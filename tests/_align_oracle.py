@@ -10,7 +10,10 @@ compiler -- a per-cell Python loop is too slow for the GPU cases) and walks them
   state E:           the same along the row.
 
 CIGAR: forward order, run-length encoded: '=' / 'X' diagonal on equal / different letters, 'I' vertical
-(a query letter only), 'D' horizontal (a subject letter only).  Nothing here knows the kernel's codes."""
+(a query letter only), 'D' horizontal (a subject letter only).  Nothing here knows the kernel's codes.
+
+NEG is finite, as in oracle/score_oracle.c, and the same range holds: global pairs within
+B + |go| < 2^29, the range the library accepts (tests/test_exact_reference.py)."""
 import ctypes
 import os
 import re

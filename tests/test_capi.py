@@ -1,9 +1,12 @@
 """The C-ABI library: loads, exports every symbol include/gsa.h declares, and its host-side
 consumers (Trace1/Hash1/Trace2/Hash2, src/nwtrace1_plain.cpp / src/nwtrace2_sparse.cpp)
-agree with the oracle.  No GPU compute here."""
+agree with the oracle; and loading it before PyTorch leaves one HIP runtime in the process.  No GPU
+compute here."""
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -86,3 +89,28 @@ def test_registry_names():
     m = gsa.get_nw_algorithm_map()
     assert m["NwAlign_Gpu9_Mlsp_DiagDiagDiag"].trace is m["NwAlign_Amd_Strip_Mlsp"].trace
     assert m["NwAlign_Gpu3_Ml_DiagDiag"].hash is m["NwAlign_Amd_Strip_Full"].hash
+
+
+_ORDER = """
+import gpuseqalign_amd as gsa
+gsa.lib()                     # the library first ...
+import torch                  # ... then PyTorch, which may bring a HIP runtime of its own
+names = {l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}
+%s
+print('runtimes', len(names))
+"""
+
+
+def test_library_before_torch_is_one_hip_runtime():
+    """gsa.lib() in a fresh process that has not imported torch yet: one libamdhip64 in the process
+    afterwards, not the system's beside PyTorch's (whichever of two initialises second finds no device)."""
+    out = subprocess.run([sys.executable, "-c", _ORDER % ""], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    assert out.split()[-2:] == ["runtimes", "1"], out
+
+
+@pytest.mark.gpu
+def test_library_before_torch_still_opens_the_device(engine):
+    """The same order on a GPU: both PyTorch and a context of ours find the device."""
+    body = "assert torch.cuda.is_available(); torch.zeros(1, device='cuda:0'); gsa.Engine(0).close()"
+    out = subprocess.run([sys.executable, "-c", _ORDER % body], cwd=ROOT, capture_output=True, text=True, check=True).stdout
+    assert out.split()[-2:] == ["runtimes", "1"], out

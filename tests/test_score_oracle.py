@@ -2,14 +2,15 @@
 SURVEY.md 8(f)3).  The reference has no implementation of these modes, so the C restatement
 is pinned here by (a) the NW-LG special case go == ge == g against orc_fill_full, itself
 pinned to the reference's known answers, (b) an independent pure-Python restatement of the
-recurrences on small pairs, and (c) the tiled OpenMP wavefront version."""
+recurrences on small pairs, with a true minus infinity where the C code has -2^29 (tests/
+test_exact_reference.py shows where the two part), and (c) the tiled OpenMP wavefront version."""
 import numpy as np
 import pytest
 
 import oracle
 from tests._data import random_pair, related_pair
 
-NEG = -(1 << 29)
+NEG = float("-inf")  # not the oracle's finite stand-in: every H that is read is a Python int
 
 
 def py_score(Y, X, sub, go, ge, local):
