@@ -238,6 +238,15 @@ SIGNATURES = {
                                               ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                               ctypes.POINTER(AlignDbMultiInfo), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_align_db_multi_unit": (_i32, []),
+    "gsa_score_db_multi_semi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32,
+                                                   _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
+                                                   ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
+                                                   ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_db_multi_semi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32,
+                                                   _i32p, _i32p, _i32, _vp, _i32, _i32, _i32, _i32, _i64,
+                                                   ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                                   ctypes.POINTER(_i64), ctypes.POINTER(AlignDbMultiInfo),
+                                                   ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score":(ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -716,6 +725,15 @@ class Engine:
         "kernel_ms"}.  Every pair's result is score_db_dev's for that query and subject.
         `max_workgroups` caps the lane kernel's grid (0: all resident), `scratch_limit` the bytes of
         results held on the device at once (0: the default).  last_score_db_multi_info() says what ran."""
+        res, self._score_db_multi_info = self._score_db_many(
+            "gsa_score_db_multi_dev", queries_ptr, q_off, db_ptr, db_off, subst_ptr, substsz, gapo, gape, (int(local),),
+            top, want_scores, max_workgroups, scratch_limit, stream)
+        return res
+
+    def _score_db_many(self, entry: str, queries_ptr, q_off, db_ptr, db_off, subst_ptr, substsz, gapo, gape, mode: tuple,
+                       top, want_scores, max_workgroups, scratch_limit, stream):
+        """The call behind score_db_multi_dev (mode = (local,)) and score_db_semi_dev (mode = ()):
+        (result dict, info dict)."""
         qo = np.ascontiguousarray(q_off, dtype=np.int64)
         off = np.ascontiguousarray(db_off, dtype=np.int64)
         nq, n = len(qo) - 1, len(off) - 1
@@ -726,16 +744,15 @@ class Engine:
         info = ScoreDbMultiInfo()
         ms = ctypes.c_float(0.0)
         i64p = ctypes.POINTER(_i64)
-        st = lib().gsa_score_db_multi_dev(
+        st = getattr(lib(), entry)(
             self._h, queries_ptr, qo.ctypes.data_as(i64p), nq, db_ptr, off.ctypes.data_as(i64p), n, subst_ptr, substsz,
-            gapo, gapo if gape is None else gape, int(local), top, int(max_workgroups), int(scratch_limit),
+            gapo, gapo if gape is None else gape, *mode, top, int(max_workgroups), int(scratch_limit),
             scores.ctypes.data_as(_i32p) if scores is not None else None,
             hits.ctypes.data_as(ctypes.POINTER(DbHit)) if hits is not None else None, ctypes.byref(info),
             ctypes.byref(ms), stream)
-        self._check(st, "gsa_score_db_multi_dev")
-        self._score_db_multi_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
-                                     for k, t in info._fields_}
-        return {"scores": scores, "hits": hits, "kernel_ms": float(ms.value)}
+        self._check(st, entry)
+        what = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k))) for k, t in info._fields_}
+        return {"scores": scores, "hits": hits, "kernel_ms": float(ms.value)}, what
 
     def last_score_db_multi_info(self) -> dict:
         """gsa_score_db_multi_info of the last score_db_multi_dev call on this engine: "lane_queries",
@@ -766,12 +783,21 @@ class Engine:
         "j_end", "cigar", "kernel_ms"}.  `max_workgroups` caps the fill's grid (0: all resident),
         `scratch_limit` the bytes of move codes held at once (0: the default).
         last_align_db_multi_info() says what the call ran."""
+        res, self._align_db_multi_info = self._align_db_many(
+            "gsa_align_db_multi_dev", queries_ptr, q_off, db_ptr, db_off, hit_query, hit_subject, subst_ptr, substsz, gapo,
+            gape, (int(local),), max_workgroups, scratch_limit, stream)
+        return res
+
+    def _align_db_many(self, entry: str, queries_ptr, q_off, db_ptr, db_off, hit_query, hit_subject, subst_ptr, substsz,
+                       gapo, gape, mode: tuple, max_workgroups, scratch_limit, stream):
+        """The call behind align_db_multi_dev (mode = (local,)) and align_db_semi_dev (mode = ()):
+        (list of result dicts, info dict)."""
         qo = np.ascontiguousarray(q_off, dtype=np.int64)
         off = np.ascontiguousarray(db_off, dtype=np.int64)
         hq = np.ascontiguousarray(hit_query, dtype=np.int32).ravel()
         hs = np.ascontiguousarray(hit_subject, dtype=np.int32).ravel()
         if len(hq) != len(hs):
-            raise NwError(NwStat.errorInvalidValue, "align_db_multi_dev: hit_query and hit_subject differ in length")
+            raise NwError(NwStat.errorInvalidValue, entry + ": hit_query and hit_subject differ in length")
         nq, n, nh = len(qo) - 1, len(off) - 1, len(hq)
         res = (AlignDbResult * max(nh, 1))()
         info = AlignDbMultiInfo()
@@ -783,14 +809,13 @@ class Engine:
             cap = int(2 * (np.diff(off)[hs].clip(1) - 1 + np.diff(qo)[hq].clip(1) - 1).sum() + nh)
         buf = ctypes.create_string_buffer(max(cap, 1))
         i64p = ctypes.POINTER(_i64)
-        st = lib().gsa_align_db_multi_dev(
+        st = getattr(lib(), entry)(
             self._h, queries_ptr, qo.ctypes.data_as(i64p), nq, db_ptr, off.ctypes.data_as(i64p), n,
             hq.ctypes.data_as(_i32p), hs.ctypes.data_as(_i32p), nh, subst_ptr, substsz, gapo,
-            gapo if gape is None else gape, int(local), int(max_workgroups), int(scratch_limit), res, buf, cap,
+            gapo if gape is None else gape, *mode, int(max_workgroups), int(scratch_limit), res, buf, cap,
             ctypes.byref(need), ctypes.byref(info), ctypes.byref(ms), stream)
-        self._check(st, "gsa_align_db_multi_dev")
-        self._align_db_multi_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
-                                     for k, t in info._fields_}
+        self._check(st, entry)
+        what = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k))) for k, t in info._fields_}
         raw = buf.raw
         out = []
         for r in res[:nh]:
@@ -798,7 +823,7 @@ class Engine:
             out.append({"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start),
                         "j_start": int(r.j_start), "i_end": int(r.i_end), "j_end": int(r.j_end), "cigar": cig,
                         "kernel_ms": float(ms.value)})
-        return out
+        return out, what
 
     def last_align_db_multi_info(self) -> dict:
         """gsa_align_db_multi_info of the last align_db_multi_dev call on this engine: "lane_hits",
@@ -851,6 +876,82 @@ class Engine:
         hs = np.ascontiguousarray(hits["subject"], dtype=np.int32).ravel()
         res = self.align_db_multi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hq, hs, dS.data_ptr(), substsz, gapo,
                                       gape, local)
+        ntop = hits.shape[1]
+        return [list(zip([int(x) for x in hs[q * ntop:(q + 1) * ntop]], res[q * ntop:(q + 1) * ntop]))
+                for q in range(hits.shape[0])]
+
+    # -- semi-global database search: the whole query within each subject --
+
+    def score_db_semi_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, subst_ptr: int, substsz: int,
+                          gapo: int, gape: Optional[int] = None, top: int = 0, want_scores: bool = True,
+                          max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None) -> dict:
+        """Many queries against a database in the semi-global shape (gsa_score_db_multi_semi_dev;
+        synchronous): every query letter aligned, the subject's head and tail free.  Arguments and
+        result as score_db_multi_dev's without `local`; a hit's (i_end, j_end) is (R, the smallest
+        column of row R that attains the score), and scores may be negative.  The mode has no second
+        path: a pair the lane kernels cannot take makes the call errorInvalidValue (include/gsa.h).
+        last_score_db_semi_info() says what ran."""
+        res, self._score_db_semi_info = self._score_db_many(
+            "gsa_score_db_multi_semi_dev", queries_ptr, q_off, db_ptr, db_off, subst_ptr, substsz, gapo, gape, (), top,
+            want_scores, max_workgroups, scratch_limit, stream)
+        return res
+
+    def last_score_db_semi_info(self) -> dict:
+        """gsa_score_db_multi_info of the last score_db_semi_dev call on this engine (the keys of
+        last_score_db_multi_info(); "other_queries" is 0)."""
+        info = getattr(self, "_score_db_semi_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_score_db_semi_info: no score_db_semi_dev call yet")
+        return dict(info)
+
+    def score_db_semi(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, top: int = 0) -> dict:
+        """score_db_semi_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front, as score_db_multi takes them."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.score_db_semi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape, top)
+
+    def align_db_semi_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, hit_query, hit_subject, subst_ptr: int,
+                          substsz: int, gapo: int, gape: Optional[int] = None, max_workgroups: int = 0,
+                          scratch_limit: int = 0, stream: Optional[int] = None) -> list:
+        """The semi-global alignments of chosen (query, subject) pairs (gsa_align_db_multi_semi_dev;
+        synchronous): arguments and result dicts as align_db_multi_dev's without `local`.  Score and
+        end cell are score_db_semi_dev's; the walk stops in row 0, so "i_start" is 0, "j_start" the
+        column where the query begins in the subject, and the CIGAR covers the query alone.  Status
+        is never 1: what the kernels cannot take makes the call errorInvalidValue.
+        last_align_db_semi_info() says what the call ran."""
+        res, self._align_db_semi_info = self._align_db_many(
+            "gsa_align_db_multi_semi_dev", queries_ptr, q_off, db_ptr, db_off, hit_query, hit_subject, subst_ptr, substsz,
+            gapo, gape, (), max_workgroups, scratch_limit, stream)
+        return res
+
+    def last_align_db_semi_info(self) -> dict:
+        """gsa_align_db_multi_info of the last align_db_semi_dev call on this engine (the keys of
+        last_align_db_multi_info(); "unsupported" is 0)."""
+        info = getattr(self, "_align_db_semi_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_db_semi_info: no align_db_semi_dev call yet")
+        return dict(info)
+
+    def align_db_semi(self, queries, subjects, hit_query, hit_subject, subst, gapo: int,
+                      gape: Optional[int] = None) -> list:
+        """align_db_semi_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front; `hit_query` indexes `queries`, `hit_subject` indexes `subjects`."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.align_db_semi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hit_query, hit_subject, dS.data_ptr(),
+                                      substsz, gapo, gape)
+
+    def search_db_semi(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, top: int = 10) -> list:
+        """Semi-global database search with alignments for many queries: one upload, one
+        score_db_semi_dev with `top` and one align_db_semi_dev on all the hits.  Per query
+        [(subject_index, result dict)], best subject first."""
+        if max(int(top), 0) == 0:
+            return [[] for _ in queries]
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        hits = self.score_db_semi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape, top,
+                                      want_scores=False)["hits"]
+        hq = np.repeat(np.arange(hits.shape[0], dtype=np.int32), hits.shape[1])
+        hs = np.ascontiguousarray(hits["subject"], dtype=np.int32).ravel()
+        res = self.align_db_semi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hq, hs, dS.data_ptr(), substsz, gapo, gape)
         ntop = hits.shape[1]
         return [list(zip([int(x) for x in hs[q * ntop:(q + 1) * ntop]], res[q * ntop:(q + 1) * ntop]))
                 for q in range(hits.shape[0])]

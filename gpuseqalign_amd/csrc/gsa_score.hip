@@ -19,6 +19,8 @@
 #include "nw_krow.h"
 #include "nw_lanes.h"
 #include "nw_lanes_multi.h"
+#include "nw_lanes_semi.h"
+#include "nw_lanes_semi_trace.h"
 #include "nw_lanes_trace.h"
 #include "nw_lanes_trace_multi.h"
 #include "nw_scan.h"
@@ -1278,6 +1280,20 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
     return GSA_SUCCESS;
 }
 
+// The semi-global calls have the lane kernels and no second path: a pair of R query
+// and C subject letters (both >= 1) is taken iff the subject is within the kernels' column range, the
+// query's profile fits the LDS a workgroup may have, and the value bound B stays below 2^18, which
+// covers the signed result key and the trace fill's 4 v + tag.  All three grow with R and with C, so
+// the longest query against the longest subject fails them iff any pair does.
+int semi_ranges(const gsa_ctx* ctx, int64_t R, int64_t C, long long smax, int32_t substsz, int32_t gapo, int32_t gape)
+{
+    if (C > gsa::kDbLanesMaxC) return GSA_ERROR_INVALID_VALUE;
+    if (R >= (1 << 20) || gsa::dblanes_lds_bytes((int)R, substsz) > (size_t)ctx->lds_max) return GSA_ERROR_INVALID_VALUE;
+    const long long B = smax * std::min(R, C) - (long long)gapo - (R + C) * (long long)gape;
+    if (B >= gsa::kDbSemiMaxValue) return GSA_ERROR_INVALID_VALUE;
+    return GSA_SUCCESS;
+}
+
 // Default of gsa_score_db_multi_dev's scratch_limit: bytes of result matrix a call holds at once.
 constexpr int64_t kDbMultiScratch = 256ll << 20;
 
@@ -1294,9 +1310,12 @@ bool offsets_ok(const int64_t* off, int32_t n)
 // Lmax through score_batch_impl per query, whole queries through score_db_impl), then one launch of
 // nw_lanes_multi.hip per sweep class over the lane subjects (sorted longest first once, for all
 // queries), the other paths' results scattered into the matrix, the ranking, and one copy back.
+// semi (gsa_score_db_multi_semi_dev, local = 0): the semi-global shape of nw_lanes_semi.hip.  There is
+// no other path for it: every pair with letters on both sides runs on the lane kernel or the call is
+// refused before anything is enqueued, and GSA_DB_LANES / GSA_DB_MAXC are not read.
 int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                         const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo,
-                        int32_t gape, int32_t local, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                        int32_t gape, int32_t local, bool semi, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
                         int32_t* scores, gsa_db_hit* hits, gsa_score_db_multi_info* info, float* kernel_ms,
                         hipStream_t st)
 {
@@ -1338,14 +1357,16 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         // score_ranges' bounds grow with R and with C: the longest query against the longest subject
         // is outside every kernel's range iff any pair is
         bool stripOk = false;
-        const int s = score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
+        const int s = semi ? semi_ranges(ctx, Rmax, Cmax, smax, substsz, gapo, gape)
+                           : score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
         if (s != GSA_SUCCESS) return s;
     }
     const KeepLaunchRecord keep(ctx);
 
     // the subjects: the lane kernel's, longest first; those with no letters; those past Lmax
-    const bool lanesOn = env_int(ctx, "GSA_DB_LANES", 1) != 0;
-    const int lmax = std::max(0, std::min(env_int(ctx, "GSA_DB_MAXC", kDbLanesLmax), gsa::kDbLanesMaxC));
+    const bool lanesOn = semi || env_int(ctx, "GSA_DB_LANES", 1) != 0;
+    const int lmax = semi ? gsa::kDbLanesMaxC
+                          : std::max(0, std::min(env_int(ctx, "GSA_DB_MAXC", kDbLanesLmax), gsa::kDbLanesMaxC));
     std::vector<int> laneS, emptyS, longS;
     for (int s = 0; s < nsubj; ++s)
     {
@@ -1365,6 +1386,8 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
     };
     auto empty_pair = [&](int64_t R, int64_t C) {
         const int64_t k = R + C;
+        // semi-global: no query letters, score 0 at (0, 0); no subject letters, R inserts ending in (R, 0)
+        if (semi) return gsa::DbLanesOut {R == 0 ? 0 : (int)(gapo + (R - 1) * gape), (int)R, 0, 0};
         return gsa::DbLanesOut {(local || k == 0) ? 0 : (int)(gapo + (k - 1) * gape), local ? 0 : (int)R, local ? 0 : (int)C, 0};
     };
 
@@ -1426,8 +1449,14 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
                 for (int sj = 0; sj < nsubj; ++sj) patch(row, sj, empty_pair(0, cols_of(sj)));
                 continue;
             }
+            if (semi && nl == 0)
+            {
+                for (int sj = 0; sj < nsubj; ++sj) patch(row, sj, empty_pair(R, 0));
+                continue;
+            }
             if (!on_lanes(R))
             {
+                if (semi) return GSA_ERROR_INVALID_VALUE;  // semi_ranges has let it through: not reached
                 res.resize((size_t)nsubj);
                 float ms = 0.f;
                 if ((s = score_db_impl(ctx, query, (int32_t)(R + 1), db, db_off, nsubj, subst, substsz, gapo, gape, local,
@@ -1485,7 +1514,8 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             const int passes = passes_of(hq[b].R);
             while (k < hq.size() && passes_of(hq[k].R) == passes) ++k;
             int wgs = 1;
-            if ((e = gsa::dbmulti_resident(passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            if ((e = semi ? gsa::dbsemi_resident(passes, substsz, gapo != gape, &wgs)
+                          : gsa::dbmulti_resident(passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             const long long nunits = (long long)(k - b) * unitsPerQuery;
             int grid = (int)std::max<long long>(1, std::min<long long>(wgs, nunits));
@@ -1526,7 +1556,8 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             a.bnd = a.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
             a.bndStride = cmax + 1;
             if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            if ((e = gsa::launch_dbmulti(a, local, grids[c], st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            if ((e = semi ? gsa::launch_dbsemi(a, grids[c], st) : gsa::launch_dbmulti(a, local, grids[c], st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             note_launch(ctx);
             inf.launches += 1;
             inf.workgroups = grids[c];
@@ -1584,10 +1615,13 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
 // nw_lanes_trace_multi_plan.h: per chunk one upload of its records, one fill launch per sweep class
 // (nw_lanes_trace_multi.hip), one walk launch over all its hits and one copy back.  The code, meta and
 // result buffers are gsa_align_db_dev's.  gsa_last_launch's record is left as it was.
+// semi (gsa_align_db_multi_semi_dev, local = 0): the semi-global shape of nw_lanes_semi_trace.hip on
+// the same plan and buffers.  No hit is status 1: a hit outside semi_ranges, or a scratch_limit below
+// the largest hit's move codes, refuses the call before anything is enqueued.
 int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                         const int64_t* db_off, int32_t nsubj, const int32_t* hit_query, const int32_t* hit_subject,
                         int32_t nhits, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
-                        int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                        bool semi, int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
                         int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_multi_info* info, float* kernel_ms,
                         hipStream_t st)
 {
@@ -1624,7 +1658,8 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         // score_ranges' bounds grow with R and with C: the longest query against the longest subject
         // is outside every kernel's range iff any pair is
         bool stripOk = false;
-        const int s = score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
+        // (semi-global: the hits alone are tested, below)
+        const int s = semi ? GSA_SUCCESS : score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
         if (s != GSA_SUCCESS) return s;
     }
     if (nhits == 0) return GSA_SUCCESS;
@@ -1640,6 +1675,24 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         const int64_t R = rows_of(hit_query[h]), C = cols_of(hit_subject[h]);
         gsa_align_db_result& r = out[h];
         std::memset(&r, 0, sizeof(r));
+        if (semi && (R == 0 || C == 0))
+        {
+            // no query letters: score 0 at (0, 0), nothing to say; no subject letters: R inserts
+            if (R > 0)
+            {
+                r.score = (int32_t)(gapo + (R - 1) * gape);
+                r.i_end = R;
+                cig[(size_t)h] = std::to_string(R) + 'I';
+            }
+            continue;
+        }
+        if (semi)
+        {
+            if (semi_ranges(ctx, R, C, smax, substsz, gapo, gape) != GSA_SUCCESS || gsa::dbtrace_code_bytes(R, C) > limit)
+                return GSA_ERROR_INVALID_VALUE;
+            lane[(size_t)h] = 1;
+            continue;
+        }
         if (R == 0 || C == 0)
         {
             const int64_t k = R + C;
@@ -1683,7 +1736,8 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             for (const gsa::DbaLaunch& L : ch.launches)
             {
                 int wgs = 1;
-                if ((e = gsa::dbtrace_multi_resident(L.passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+                if ((e = semi ? gsa::dbsemi_trace_resident(L.passes, substsz, gapo != gape, &wgs)
+                              : gsa::dbtrace_multi_resident(L.passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
                     return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
                 int grid = std::max(1, std::min(wgs, L.nunits));
                 if (max_workgroups > 0) grid = std::min(grid, max_workgroups);
@@ -1763,7 +1817,8 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
                 a.bnd = L.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
                 a.bndStride = ch.cmax + 1;
                 if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                if ((e = gsa::launch_dbtrace_multi_fill(a, local, grids[c][l], st)) != hipSuccess)
+                if ((e = semi ? gsa::launch_dbsemi_trace_fill(a, grids[c][l], st)
+                              : gsa::launch_dbtrace_multi_fill(a, local, grids[c][l], st)) != hipSuccess)
                     return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
                 note_launch(ctx);
                 inf.launches += 1;
@@ -1785,7 +1840,8 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             w.moveOff = (const long long*)(meta + moffAt);
             w.res = (gsa::DbTraceOut*)adbres;
             w.moves = adbres + movAt;
-            if ((e = gsa::launch_dbtrace_multi_walk(w, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            if ((e = semi ? gsa::launch_dbsemi_trace_walk(w, st) : gsa::launch_dbtrace_multi_walk(w, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             (void)hipEventRecord(ctx->adbev[2], st);
             if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)ch.moveBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
                 (e = hipStreamSynchronize(st)) != hipSuccess)
@@ -1889,7 +1945,20 @@ int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
-                               gapo, gape, local, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need, info,
+                               gapo, gape, local, false, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need,
+                               info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                const int32_t* db, const int64_t* db_off, int32_t nsubj, const int32_t* hit_query,
+                                const int32_t* hit_subject, int32_t nhits, const int32_t* subst, int32_t substsz,
+                                int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
+                                gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                gsa_align_db_multi_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
+                               gapo, gape, 0, true, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need, info,
                                kernel_ms, pick_stream(ctx, stream));
 }
 
@@ -1902,7 +1971,18 @@ int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
                            void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, local, top,
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, local, false, top,
+                               max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                const int32_t* db, const int64_t* db_off, int32_t nsubj, const int32_t* subst,
+                                int32_t substsz, int32_t gapo, int32_t gape, int32_t top, int32_t max_workgroups,
+                                int64_t scratch_limit, int32_t* scores, gsa_db_hit* hits, gsa_score_db_multi_info* info,
+                                float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, 0, true, top,
                                max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
 }
 

@@ -589,6 +589,67 @@ int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
                            gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
 /* Wave tasks (of up to four hits) in a unit of gsa_align_db_multi_dev: a compile-time constant. */
 int32_t gsa_align_db_multi_unit(void);
+
+/* Database search, semi-global mode: the whole query within each subject.
+ * The alignment shape is neither of gsa_score_db_multi_dev's two: every query letter is aligned, and
+ * the subject's unaligned head and tail cost nothing (an adapter, primer or barcode in every read, a
+ * domain in every protein).  With R query and C subject letters and the Gotoh recurrences of
+ * "score-only NW / SW" above, without the zero floor:
+ *   row 0 is free:        H(0, j) = 0, E(0, j) = F(0, j) = minus infinity, j = 0 ... C;
+ *   column 0 is global:   H(i, 0) = F(i, 0) = gapo + (i - 1) gape, E(i, 0) = minus infinity, i >= 1;
+ *   score = max over j = 0 ... C of H(R, j) -- column 0, the all-insert alignment, is a candidate;
+ *   end cell: i_end = R, j_end the SMALLEST j that attains the score.
+ * Scores may be negative.  A subject without letters against a query with some: score
+ * gapo + (R - 1) gape, end cell (R, 0); a query without letters: score 0, end cell (0, 0); both are
+ * answered on the host.
+ *
+ * gsa_score_db_multi_semi_dev takes gsa_score_db_multi_dev's arguments without local; queries, q_off,
+ * nq, db, db_off, nsubj, subst, substsz, gapo, gape, top, max_workgroups, scratch_limit, scores, hits,
+ * info, kernel_ms and stream mean what they mean there: the same chunks of result rows, the same
+ * ranking by (score descending, subject index ascending) on the device, the same device buffers
+ * (counted in gsa_mem_stats).  *info is a gsa_score_db_multi_info with other_queries = 0.  The pairs run
+ * on nw_lanes_semi.hip, one persistent launch per sweep class with gsa_score_db_multi_unit() tasks per
+ * unit.
+ * This mode has no second path: a pair runs on the lane kernels or the call is refused.  It is
+ * errorInvalidValue, before anything is enqueued, when any (query, subject) pair with letters on both
+ * sides has a subject of more than 8191 letters, a query whose profile (4 substsz (384 ceil(R / 384) + 4)
+ * bytes) does not fit the LDS a workgroup may have, or a value bound
+ * B = smax min(R, C) + |gapo| + (R + C) |gape| >= 2^18 (smax: the largest |table value|); as all
+ * three grow with R and C, the longest query against the longest subject decides.  GSA_DB_MAXC and
+ * GSA_DB_LANES do not apply.  Everything gsa_score_db_multi_dev rejects is rejected here too.  The call
+ * adds no launch kind and no knob: the record of gsa_last_launch is left untouched and the fills'
+ * sticky error word is left alone. */
+int gsa_score_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                                const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                                int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                                int32_t* scores, gsa_db_hit* hits,
+                                gsa_score_db_multi_info* info, float* kernel_ms, void* stream);
+
+/* The semi-global alignments of nhits (query, subject) pairs, traced on the device: the arguments of
+ * gsa_align_db_multi_dev without local, the same result struct, CIGAR buffer rules (strings back to
+ * back in hit order, status 2 for one that does not fit, *cigar_need), chunks by scratch_limit
+ * (0: 256 MiB), *info and *kernel_ms.
+ * Semantics: score and end cell (R, j_end) are gsa_score_db_multi_semi_dev's for the pair.  The walk
+ * goes backwards from (R, j_end) in state H under gsa_align_db_dev's rules -- diagonal before F before
+ * E at equal value, a gap extended only when that is strictly better than opening, column 0 F only --
+ * and stops as soon as it is in row 0: i_start = 0, j_start the column it stopped in; no 'D' is
+ * emitted in row 0, so the subject's head and tail stay out of the CIGAR.  A subject without letters
+ * gives R x 'I' from (0, 0) to (R, 0); a query without letters score 0, all cells (0, 0) and an empty
+ * CIGAR; both on the host.
+ * No hit is status 1 (info->unsupported = 0): the call is errorInvalidValue, before anything is
+ * enqueued, when a hit with letters on both sides fails one of gsa_score_db_multi_semi_dev's three
+ * tests (evaluated over the hits only), or when scratch_limit is below the largest hit's move codes
+ * (192 ceil(R / 384) (C + 1) bytes).  Everything gsa_align_db_multi_dev rejects is rejected here too.
+ * The fill and the walk are nw_lanes_semi_trace.hip's on gsa_align_db_multi_dev's plan and buffers.  The
+ * call adds no launch kind and no knob and leaves the record of gsa_last_launch untouched. */
+int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                                const int32_t* hit_query, const int32_t* hit_subject, int32_t nhits,
+                                const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                                int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
+                                char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
