@@ -133,6 +133,13 @@ class AlignDbInfo(ctypes.Structure):
                 ("walk_ms", ctypes.c_float)]
 
 
+class AlignPairInfo(ctypes.Structure):
+    """gsa_align_pair_info (include/gsa.h): what the last gsa_align_pair_dev call ran."""
+    _fields_ = [("strip_rows", ctypes.c_int32), ("strips", ctypes.c_int32), ("strips_filled", ctypes.c_int32),
+                ("chunks", ctypes.c_int32), ("code_bytes", ctypes.c_int64), ("score_ms", ctypes.c_float),
+                ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("pad0", ctypes.c_int32)]
+
+
 class DbHit(ctypes.Structure):
     """gsa_db_hit (include/gsa.h): one ranked subject of a query of gsa_score_db_multi_dev."""
     _fields_ = [("subject", ctypes.c_int32), ("score", ctypes.c_int32), ("i_end", ctypes.c_int32),
@@ -228,6 +235,9 @@ SIGNATURES = {
                                         _i32, _i32, _i64, ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
                                         ctypes.POINTER(_i64), ctypes.POINTER(AlignDbInfo),
                                         ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_pair_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i64,
+                                          ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                          ctypes.POINTER(AlignPairInfo), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_multi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32, _vp,
                                               _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
                                               ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
@@ -710,6 +720,59 @@ class Engine:
         if not order:
             return []
         return list(zip(order, self.align_db(query, subjects, order, subst, gapo, gape, local)))
+
+    # -- the alignment of one long pair, traced on the device -----------------
+
+    def align_pair_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int, substsz: int,
+                       gapo: int, gape: Optional[int] = None, local: bool = False, scratch_limit: int = 0,
+                       stream: Optional[int] = None) -> dict:
+        """The alignment of one device-resident pair of any length the K-rows score kernel takes
+        (gsa_align_pair_dev; synchronous): the arguments of score_dev, and `scratch_limit`, the bytes
+        of move codes held at once (0: the default, 2 GiB).  {"score", "status", "i_start",
+        "j_start", "i_end", "j_end", "cigar", "kernel_ms"} as align_db_dev returns per hit; status 0
+        aligned, 1 score and end cell only ("cigar" is "").  last_align_pair_info() says what ran."""
+        res = AlignDbResult()
+        info = AlignPairInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes always suffice
+        cap = 2 * (max(adjrows - 1, 0) + max(adjcols - 1, 0)) + 1
+        buf = ctypes.create_string_buffer(cap)
+        st = lib().gsa_align_pair_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                      gapo if gape is None else gape, int(local), int(scratch_limit),
+                                      ctypes.byref(res), buf, cap, ctypes.byref(need), ctypes.byref(info),
+                                      ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_pair_dev")
+        self._align_pair_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                 for k, t in info._fields_ if k != "pad0"}
+        cig = buf.raw[res.cigar_off:res.cigar_off + res.cigar_len].decode() if res.status == 0 else ""
+        return {"score": int(res.score), "status": int(res.status), "i_start": int(res.i_start),
+                "j_start": int(res.j_start), "i_end": int(res.i_end), "j_end": int(res.j_end), "cigar": cig,
+                "kernel_ms": float(ms.value)}
+
+    def last_align_pair_info(self) -> dict:
+        """gsa_align_pair_info of the last align_pair_dev call on this engine: "strip_rows" (the score
+        kernel's ticket, 0 when it did not run), "strips" up to the end cell's row, "strips_filled",
+        "chunks" (fill + walk launch pairs), "code_bytes" (peak bytes of move codes held at once),
+        "score_ms", "fill_ms" and "walk_ms"."""
+        info = getattr(self, "_align_pair_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_pair_info: no align_pair_dev call yet")
+        return dict(info)
+
+    def align_pair(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
+                   scratch_limit: int = 0) -> dict:
+        """align_pair_dev over host arrays: the sequences with the header element in front, as score()
+        takes them; sequences and table are uploaded through torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return self.align_pair_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz, gapo,
+                                   gape, local, scratch_limit)
 
     # -- many queries against one database in one call (DESIGN.md 2.2f) ----------------------
 

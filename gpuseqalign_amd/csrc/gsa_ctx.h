@@ -153,6 +153,11 @@ enum BufId
     kBufDbmOut,
     kBufDbmRes,
     kBufDbmSel,
+    // the alignment of one long pair (gsa_align_pair_dev): the move codes of one chunk of strips; the
+    // fill's task counter and the walk's record; the move bytes
+    kBufPairCodes,
+    kBufPairMeta,
+    kBufPairMoves,
     // mlsppt: host-mapped per-tile-row words (epoch << 32 | column chunks in memory); a pinned host
     // buffer (>= kPtPin) the strided column chunks are packed into by copies on ptstream
     kBufPtFlags,  // mapped host memory
@@ -218,7 +223,7 @@ struct gsa_ctx
     hipEvent_t ptev[2] = {nullptr, nullptr};
     static constexpr size_t kPtPin = 64u << 20;  // two slots
     hipStream_t ptstream = nullptr;
-    hipEvent_t adbev[3] = {nullptr, nullptr, nullptr};  // gsa_align_db_dev: around the fill and the walk
+    hipEvent_t adbev[3] = {nullptr, nullptr, nullptr};  // gsa_align_db_dev, gsa_align_pair_dev: around the fill and the walk
     hipEvent_t dbmev[4] = {nullptr, nullptr, nullptr, nullptr};  // gsa_score_db_multi_dev: the lane launches, the ranking
     // copy-back of the host-buffer entry points into pageable caller memory: per copy thread a
     // stream and two pinned chunks (DMA of chunk k+1 overlaps the host copy of chunk k)

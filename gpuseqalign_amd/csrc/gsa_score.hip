@@ -23,6 +23,8 @@
 #include "nw_lanes_semi_trace.h"
 #include "nw_lanes_trace.h"
 #include "nw_lanes_trace_multi.h"
+#include "nw_pair_trace.h"
+#include "nw_pair_trace_plan.h"
 #include "nw_scan.h"
 #include "nw_strip.h"
 
@@ -310,8 +312,20 @@ int score_bidi(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX
     return GSA_SUCCESS;
 }
 
+// What a one-direction launch of score_ag_strip ran (gsa_align_pair_dev reads the checkpoint rows
+// the K-rows kernel left in kBufGran: row t at t gran_stride(C), the affine second array `tickets`
+// rows behind).
+struct ScoreRoute
+{
+    bool krow = false;  // the K-rows score kernel (else the strip kernel)
+    int K = 0;          // its rows per lane
+    int64_t tickets = 0;
+};
+
+// route (may be null): no split from both ends for this call, and what ran instead
 int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX, int64_t C, const int32_t* subst,
-                   int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, hipStream_t st)
+                   int32_t substsz, int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, hipStream_t st,
+                   ScoreRoute* route = nullptr)
 {
     // the K-rows score kernel's rows per lane, tickets of 64 K NS rows: 2 in the modes with the
     // longer step (SW tracking, affine gaps: the block's fixed part is a smaller share there, and
@@ -332,7 +346,7 @@ int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* 
     // 2.11 ms, profiles/r05_bidi_ab.txt).  GSA_SCORE_BIDI: 0 never, 2 at any size (tests)
     // A pair whose R is not a multiple of K but whose C is runs transposed (X down the rows, Y along
     // them, the table transposed: the same global score, and gaps cost the same either way).
-    const int bidi = env_int(ctx, "GSA_SCORE_BIDI", 1);
+    const int bidi = route ? 0 : env_int(ctx, "GSA_SCORE_BIDI", 1);
     const int kb = kenv == 2 || kenv == 4 ? kenv : 2;
     const int64_t TRb = (int64_t)(64 * kb) * gsa::kSparseNS;
     auto splits = [&](int64_t rows) { return rows % kb == 0 && rows >= 2 * kb && (bidi == 2 || rows >= 8 * TRb); };
@@ -345,6 +359,12 @@ int score_ag_strip(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* 
     }
     // local: from both ends only by rows (the end cell's row-major tie rule does not survive a
     // transpose), and back to one direction when an alignment through the split may decide it
+    if (route)
+    {
+        route->krow = krow;
+        route->K = scoreK;
+        route->tickets = tickets;
+    }
     float bidiMs = 0.f;
     if (krow && local && bidi != 0 && env_int(ctx, "GSA_SCORE_BIDI_SW", 1) && splits(R))
     {
@@ -1932,9 +1952,218 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
     return GSA_SUCCESS;
 }
 
+// gsa_align_pair_dev: the score from the K-rows score kernel in one direction (score_ag_strip with a
+// route), whose checkpoint rows stay in kBufGran; then, bottom-up, chunks of strips whose move codes
+// fit scratch_limit (nw_pair_trace_plan.h), a fill and a walk launch per chunk and one small copy of
+// the walk's record back (nw_pair_trace.hip); at the end the move bytes, folded into the CIGAR.  A
+// pair the K-rows kernel or the 4 v + tag form does not take, or whose single strip exceeds the
+// limit, gets its score and end cell and status 1.  gsa_last_launch's record is left as it was.
+int align_pair_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                    const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                    int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                    gsa_align_pair_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_pair_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : (int64_t)gsa::kPairTraceScratch;
+    gsa_align_db_result r;
+    std::memset(&r, 0, sizeof(r));
+    std::string cig;
+    if (R == 0 || C == 0)
+    {
+        // one boundary, answered on the host as align_db_impl answers it
+        const int64_t k = R + C;
+        if (!local && k > 0)
+        {
+            r.score = (int32_t)(gapo + (k - 1) * gape);
+            r.i_end = R;
+            r.j_end = C;
+            cig = std::to_string(k) + (R > 0 ? 'I' : 'D');
+        }
+    }
+    else
+    {
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        const long long smax = subst_absmax(sub.data(), substsz);
+        bool stripOk = false;
+        if ((s = score_ranges(R, C, smax, gapo, gape, local, &stripOk)) != GSA_SUCCESS) return s;
+        const KeepLaunchRecord keep(ctx);
+        // the fill keeps 4 x value + source: |H| <= smax min(R, C) + |go| + (R + C) |ge| (score_ranges' bound)
+        const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+        gsa_score_result sr {};
+        ScoreRoute route;
+        bool have = false;
+        if (valOk && stripOk && !score_scan_forced(ctx))
+        {
+            s = score_ag_strip(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, local, &sr, st, &route);
+            if (s == GSA_SUCCESS)
+                have = true;
+            else if (s != kScoreTooLarge)
+                return s;
+        }
+        if (!have)
+        {
+            // the ordinary score path, whatever it takes for this pair
+            route = ScoreRoute {};
+            if ((s = score_dev_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, local, &sr, st, smax)) !=
+                GSA_SUCCESS)
+                return s;
+        }
+        inf.score_ms = sr.calc_kernel_ms;
+        r.score = sr.score;
+        r.i_end = sr.i_end;
+        r.j_end = sr.j_end;
+        r.status = 1;
+        const int K = route.K;
+        if (have && route.krow && (K == 2 || K == 4))
+        {
+            const int KR = K * gsa::kSparseNS;
+            const int64_t TR = 64 * (int64_t)KR;
+            inf.strip_rows = (int32_t)TR;
+            if (local && sr.score == 0)
+                r.status = 0;  // no positive cell: (0, 0), an empty CIGAR
+            else
+            {
+                const int64_t iEnd = sr.i_end, jEnd = sr.j_end;
+                const int64_t strips = gsa::pair_strips(TR, iEnd);
+                inf.strips = (int32_t)strips;
+                gsa::PairChunk ch;
+                if (iEnd >= 1 && jEnd >= 1 && gsa::pair_plan_chunk(TR, strips - 1, jEnd, limit, &ch))
+                {
+                    if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
+                        (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(iEnd + jEnd), 4096)) != GSA_SUCCESS)
+                        return s;
+                    for (hipEvent_t& ev : ctx->adbev)
+                        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+                    char* const meta = ctx->buf[kBufPairMeta].as<char>();
+                    gsa::PairWalkRec* const drec = (gsa::PairWalkRec*)(meta + 64);
+                    const size_t stride = (size_t)gsa::gran_stride((int)C);
+                    gsa::PairWalkRec rec;
+                    std::memset(&rec, 0, sizeof(rec));
+                    rec.i = (int)iEnd;
+                    rec.j = (int)jEnd;
+                    rec.state = 4u;
+                    if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
+                        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                    for (;;)
+                    {
+                        const int nstrips = (int)(ch.tHi - ch.tLo + 1);
+                        if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
+                        if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                        gsa::PairFillArgs f;
+                        std::memset(&f, 0, sizeof(f));
+                        f.seqY = seqY;
+                        f.seqX = seqX;
+                        f.subst = subst;
+                        f.substsz = substsz;
+                        f.go = gapo;
+                        f.ge = gape;
+                        f.local = local ? 1 : 0;
+                        f.R = (int)R;
+                        f.iEnd = (int)iEnd;
+                        f.J = (int)ch.J;
+                        f.tLo = (int)ch.tLo;
+                        f.nstrips = nstrips;
+                        f.gran = ctx->buf[kBufGran].as<unsigned long long>();
+                        f.gran2 = f.gran + (size_t)route.tickets * stride;
+                        f.granStride = (long long)stride;
+                        f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
+                        f.stripBytes = ch.stripBytes;
+                        f.counter = (unsigned*)meta;
+                        gsa::PairWalkArgs w;
+                        std::memset(&w, 0, sizeof(w));
+                        w.seqY = seqY;
+                        w.seqX = seqX;
+                        w.codes = f.codes;
+                        w.stripBytes = ch.stripBytes;
+                        w.krShift = KR == 8 ? 3 : 4;
+                        w.tLo = (int)ch.tLo;
+                        w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
+                        w.local = f.local;
+                        w.rec = drec;
+                        w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+                        int grid = 1;
+                        if ((e = gsa::pair_fill_grid(f.local, gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
+                            (e = gsa::launch_pair_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
+                            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                        note_launch(ctx);
+                        if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                            (e = hipStreamSynchronize(st)) != hipSuccess)
+                            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                        float m0 = 0.f, m1 = 0.f;
+                        (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+                        (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+                        inf.fill_ms += m0;
+                        inf.walk_ms += m1;
+                        inf.chunks += 1;
+                        inf.strips_filled += nstrips;
+                        inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
+                        if (rec.n < 0 || rec.n > iEnd + jEnd) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                        if (rec.done) break;
+                        // on the chunk's upper boundary: the next chunk, for the columns up to here
+                        if (ch.tLo < 1 || rec.i != w.iStop || rec.j < 1 || rec.j > ch.J ||
+                            !gsa::pair_plan_chunk(TR, ch.tLo - 1, rec.j, limit, &ch))
+                            return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                    }
+                    std::vector<unsigned char> mv((size_t)rec.n + 1);
+                    if (rec.n > 0 &&
+                        ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) !=
+                             hipSuccess ||
+                         (e = hipStreamSynchronize(st)) != hipSuccess))
+                        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                    cig = fold_cigar(mv.data(), rec.n);
+                    r.i_start = rec.i;
+                    r.j_start = rec.j;
+                    r.status = 0;
+                }
+            }
+        }
+    }
+    const int64_t len = (int64_t)cig.size();
+    if (r.status == 0)
+    {
+        if (len + 1 <= cigar_cap)
+        {
+            std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
+            r.cigar_len = len;
+        }
+        else
+            r.status = 2;
+        if (cigar_need) *cigar_need = len + 1;
+    }
+    *out = r;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_align_pair_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                       int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                       int64_t* cigar_need, gsa_align_pair_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_pair_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, local, scratch_limit, out, cigar,
+                           cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
 
 int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                            const int64_t* db_off, int32_t nsubj, const int32_t* hit_query, const int32_t* hit_subject,

@@ -486,6 +486,54 @@ int gsa_align_db_dev(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int
                      char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_info* info,
                      float* kernel_ms, void* stream);
 
+/* The alignment of one long pair. */
+typedef struct gsa_align_pair_info {  /* what the call ran; optional out-parameter */
+    int32_t strip_rows;     /* TR: rows of a strip, the score kernel's ticket (512 or 1024); 0: that kernel did not run */
+    int32_t strips;         /* strips that hold the rows 1 ... i_end */
+    int32_t strips_filled;  /* strips filled with move codes, over all chunks */
+    int32_t chunks;         /* fill + walk launch pairs */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    float score_ms, fill_ms, walk_ms; /* hipEvent time of the score launch, and of the fill and the walk launches
+                                         summed over the chunks */
+    int32_t pad0;
+} gsa_align_pair_info;
+
+/* The alignment of one pair of any length the K-rows score kernel takes, traced on the device.  seqY
+ * (the query, down the rows), adjrows, seqX (the subject, along the columns), adjcols, subst, substsz,
+ * gapo, gape, local: exactly as gsa_score_dev takes them.  out is one host result.  Synchronous.
+ * Semantics: gsa_align_db_dev's, word for word -- the recurrences, boundaries and end cell of
+ * gsa_score_dev (score, i_end and j_end are what gsa_score_dev returns for the same arguments; local:
+ * the first maximal cell in row-major order), the walk from the end cell in state H with diagonal
+ * before F before E and a gap extended only when that is strictly better than opening, i_start /
+ * j_start, the CIGAR letters '=', 'X', 'I', 'D', and the CIGAR buffer rules: one NUL-terminated string
+ * at cigar[0], status 2 when it does not fit cigar_cap (the cells are still valid), *cigar_need (may be
+ * null) the bytes it needs, 2 (R + C) + 1 always enough.  A pair with an empty side is answered on
+ * the host as gsa_align_db_dev answers it.
+ * How: the K-rows score kernel runs the pair in one direction (no split from both ends) and leaves
+ * the bottom row of each of its tickets of TR rows (512, NW with linear gaps 1024) in its hand-off
+ * rows.  With those exact, every strip of TR rows is independent: the strips from i_end's upwards are
+ * refilled with 4-bit move codes, one wave per strip, all at once (nw_pair_trace.hip), and one lane
+ * walks the codes.  A strip's codes over the columns 1 ... j_end take j_end x TR / 2 bytes.
+ * scratch_limit is the bytes of codes the call may hold at once; 0 is the default, 2 GiB (a
+ * 64k x 64k pair).  When the strips do not all fit they are taken bottom-up in chunks of consecutive
+ * strips, a fill and a walk launch and one small copy back per chunk; a later chunk is filled only
+ * up to the column where the walk left the one below, and a local walk that ends inside a chunk
+ * ends the call.  The scratch is counted in the peaks of gsa_mem_stats.
+ * Status 1 -- score and end cell from gsa_score_dev's path, no CIGAR: a pair the K-rows score kernel
+ * does not run (a table outside int16 after the shift, a local score of 2^26 or more, a local pair
+ * the strip kernels do not take, LDS, GSA_SCORE_KERNEL=strip, GSA_SCORE_SCAN=1), a pair whose value
+ * bound (largest |table value| x the shorter length + |gapo| + (R + C) |gape|) reaches 2^26, a pair
+ * whose single strip exceeds scratch_limit.  No score depends on the route.
+ * Everything gsa_score_dev rejects (its value range included), a negative scratch_limit or cigar_cap,
+ * a null out, a null cigar with cigar_cap > 0 or a null context is errorInvalidValue before anything
+ * is enqueued.  *info (may be null) says what the call ran.  This call adds no launch kind and no
+ * knob: the record of gsa_last_launch is left untouched.  *kernel_ms (may be null) gets the hipEvent
+ * time of all kernels of the call. */
+int gsa_align_pair_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
+                       int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                       int64_t* cigar_need, gsa_align_pair_info* info, float* kernel_ms, void* stream);
+
 /* Many queries against one database in one call. */
 typedef struct gsa_db_hit { int32_t subject, score, i_end, j_end; } gsa_db_hit;
 
