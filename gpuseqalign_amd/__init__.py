@@ -140,6 +140,15 @@ class AlignPairInfo(ctypes.Structure):
                 ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("pad0", ctypes.c_int32)]
 
 
+class AlignBatchInfo(ctypes.Structure):
+    """gsa_align_batch_info (include/gsa.h): what the last gsa_align_batch_dev call ran."""
+    _fields_ = [("batch_pairs", ctypes.c_int32), ("alone_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32),
+                ("strip_rows", ctypes.c_int32), ("strips", ctypes.c_int32), ("strips_filled", ctypes.c_int32),
+                ("rounds", ctypes.c_int32), ("pad0", ctypes.c_int32), ("code_bytes", ctypes.c_int64),
+                ("score_ms", ctypes.c_float), ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float),
+                ("pad1", ctypes.c_int32)]
+
+
 class DbHit(ctypes.Structure):
     """gsa_db_hit (include/gsa.h): one ranked subject of a query of gsa_score_db_multi_dev."""
     _fields_ = [("subject", ctypes.c_int32), ("score", ctypes.c_int32), ("i_end", ctypes.c_int32),
@@ -238,6 +247,9 @@ SIGNATURES = {
     "gsa_align_pair_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i64,
                                           ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                           ctypes.POINTER(AlignPairInfo), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32, _i32, _i64,
+                                           ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                           ctypes.POINTER(AlignBatchInfo), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_multi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32, _vp,
                                               _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
                                               ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
@@ -773,6 +785,70 @@ class Engine:
         torch.cuda.synchronize(dev)
         return self.align_pair_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz, gapo,
                                    gape, local, scratch_limit)
+
+    # -- the alignments of a batch of long pairs in one call -----------------
+
+    def align_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                        local: bool = False, max_workgroups: int = 0, scratch_limit: int = 0,
+                        stream: Optional[int] = None) -> list:
+        """The alignments of many device-resident long pairs, traced on the device together
+        (gsa_align_batch_dev; synchronous).  `pairs`: sequence of (seqY_ptr, adjrows, seqX_ptr,
+        adjcols), as score_batch_dev takes it.  One dict per pair, in order, with align_pair_dev's keys
+        and, "kernel_ms" apart (the hipEvent time of the whole call's kernels in every dict), its
+        values for that pair alone.  `max_workgroups` caps the grids of the fill and of the walk (0: all
+        resident), `scratch_limit` the bytes of move codes held at once (0: the default, 8 GiB).
+        last_align_batch_info() says what ran."""
+        n = len(pairs)
+        arr = (PairDev * max(n, 1))()
+        cap = 0
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+            cap += 2 * (max(ar - 1, 0) + max(ac - 1, 0)) + 1  # 2 (R + C) + 1 bytes always suffice
+        res = (AlignDbResult * max(n, 1))()
+        info = AlignBatchInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        st = lib().gsa_align_batch_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                       int(local), int(max_workgroups), int(scratch_limit), res, buf, cap,
+                                       ctypes.byref(need), ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_batch_dev")
+        self._align_batch_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                  for k, t in info._fields_ if not k.startswith("pad")}
+        raw = buf.raw
+        return [{"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start), "j_start": int(r.j_start),
+                 "i_end": int(r.i_end), "j_end": int(r.j_end),
+                 "cigar": raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else "",
+                 "kernel_ms": float(ms.value)} for r in res[:n]]
+
+    def last_align_batch_info(self) -> dict:
+        """gsa_align_batch_info of the last align_batch_dev call on this engine: "batch_pairs" (traced
+        by the batched route), "alone_pairs" (passed on to align_pair_dev's path), "host_pairs",
+        "strip_rows", "strips" over all batch pairs up to each end cell's row, "strips_filled", "rounds"
+        (fill + walk launch pairs), "code_bytes" (peak bytes of move codes held at once), "score_ms",
+        "fill_ms" and "walk_ms"."""
+        info = getattr(self, "_align_batch_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_batch_info: no align_batch_dev call yet")
+        return dict(info)
+
+    def align_batch(self, pairs, subst, gapo: int, gape: Optional[int] = None, local: bool = False,
+                    scratch_limit: int = 0) -> list:
+        """align_batch_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the header
+        element in front, as score_batch() takes them; sequences and table are uploaded through torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS = up(subst.ravel())
+        keep, ptrs = [], []
+        for y, x in pairs:
+            dY, dX = up(y), up(x)
+            keep.append((dY, dX))
+            ptrs.append((dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel()))
+        torch.cuda.synchronize(dev)
+        return self.align_batch_dev(ptrs, dS.data_ptr(), substsz, gapo, gape, local, 0, scratch_limit)
 
     # -- many queries against one database in one call (DESIGN.md 2.2f) ----------------------
 

@@ -158,6 +158,10 @@ enum BufId
     kBufPairCodes,
     kBufPairMeta,
     kBufPairMoves,
+    // the alignments of a batch of long pairs (gsa_align_batch_dev; codes and moves in the two slots
+    // above): a round's task counter, task, pair and walk tables; the pairs' walk records
+    kBufPairBatchTab,
+    kBufPairBatchRec,
     // mlsppt: host-mapped per-tile-row words (epoch << 32 | column chunks in memory); a pinned host
     // buffer (>= kPtPin) the strided column chunks are packed into by copies on ptstream
     kBufPtFlags,  // mapped host memory

@@ -1,6 +1,6 @@
 // gsa_score.hip -- the score-only and database entry points of libgsa.so (declared in include/gsa.h):
 // gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev, gsa_score_db_multi_dev,
-// gsa_align_db_dev and gsa_align_db_multi_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
+// gsa_align_db_dev, gsa_align_db_multi_dev, gsa_align_pair_dev and gsa_align_batch_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
 // (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
 // nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip).  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
@@ -24,6 +24,8 @@
 #include "nw_lanes_trace.h"
 #include "nw_lanes_trace_multi.h"
 #include "nw_pair_trace.h"
+#include "nw_pair_trace_batch.h"
+#include "nw_pair_trace_batch_plan.h"
 #include "nw_pair_trace_plan.h"
 #include "nw_scan.h"
 #include "nw_strip.h"
@@ -625,8 +627,23 @@ int score_dev_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int
 // gsa_score_batch_dev: the pairs the K-rows score kernel holds in one persistent launch (their
 // tickets in one ticket space, two result words per pair, decoded on the device), the others -- and
 // those the kernel flags -- one by one through score_dev_impl.
+// What score_batch_impl's launch ran (gsa_align_batch_dev reads the checkpoint rows it left in
+// kBufGran: pair p's row t at granOff[p] + t gran_stride(C), the affine second array granTotal words
+// behind).
+struct BatchScoreRoute
+{
+    int K = 0;                       // rows per lane of the K-rows launch; 0: nothing was launched
+    long long granTotal = 0;         // words of the first array, over all pairs
+    std::vector<char> inBatch;       // per pair of the call: it ran in that launch and came back unflagged
+    std::vector<int> tickets;        // its tickets there
+    std::vector<long long> granOff;  // its first row, in words
+};
+
+// route (may be null): what the launch ran; the pairs that did not run in it or came back flagged are
+// then left unscored (inBatch 0), so that nothing overwrites kBufGran before the caller has read it
 int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
-                     int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_ms, hipStream_t st)
+                     int32_t gapo, int32_t gape, int32_t local, gsa_score_result* out, float* batch_ms, hipStream_t st,
+                     BatchScoreRoute* route = nullptr)
 {
     if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
     if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
@@ -634,6 +651,13 @@ int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
     for (int p = 0; p < npairs; ++p)
         if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
     if (batch_ms) *batch_ms = 0.f;
+    if (route)
+    {
+        *route = BatchScoreRoute {};
+        route->inBatch.assign((size_t)npairs, 0);
+        route->tickets.assign((size_t)npairs, 0);
+        route->granOff.assign((size_t)npairs, 0);
+    }
     // empty pairs: one boundary, nothing to fill (score_dev_impl)
     std::vector<int> work;
     for (int p = 0; p < npairs; ++p)
@@ -805,8 +829,20 @@ int score_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
             r.score = o.score;
             r.i_end = o.i_end;
             r.j_end = o.j_end;
+            if (route)
+            {
+                route->inBatch[(size_t)bp[(size_t)i]] = 1;
+                route->tickets[(size_t)bp[(size_t)i]] = hd[(size_t)i].nTickets;
+                route->granOff[(size_t)bp[(size_t)i]] = hd[(size_t)i].granOff;
+            }
+        }
+        if (route)
+        {
+            route->K = scoreK;
+            route->granTotal = gran;
         }
     }
+    if (route) alone.clear();
     for (int p : alone)
     {
         int s = score_dev_impl(ctx, pairs[p].seqY, pairs[p].adjrows, pairs[p].seqX, pairs[p].adjcols, subst, substsz, gapo,
@@ -2151,6 +2187,337 @@ int align_pair_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const in
     return GSA_SUCCESS;
 }
 
+// gsa_align_batch_dev: the pairs' scores from score_batch_impl's launch (with a route), whose
+// checkpoint rows stay in kBufGran, every pair's at its own granOff; then rounds of one fill launch
+// over the strips of many pairs, one walk launch and one copy of the walks' records back
+// (nw_pair_trace_batch_plan.h, nw_pair_trace_batch.hip), while those rows are still there; at the end
+// the move bytes of all pairs in one copy, folded into the CIGARs.  The pairs that launch did not run
+// or flagged go through align_pair_impl afterwards, one by one: that call overwrites kBufGran and
+// reuses the kBufPair* slots.  gsa_last_launch's record is left as it was.
+int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                     int32_t gapo, int32_t gape, int32_t local, int32_t max_workgroups, int64_t scratch_limit,
+                     gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                     gsa_align_batch_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+    if (scratch_limit < 0 || cigar_cap < 0 || max_workgroups < 0 || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_batch_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : (int64_t)gsa::kPairBatchScratch;
+    std::vector<gsa_align_db_result> res((size_t)npairs);
+    std::memset(res.data(), 0, res.size() * sizeof(gsa_align_db_result));
+    std::vector<std::string> cig((size_t)npairs);
+    float other_ms = 0.f;
+    // pairs with an empty side: one boundary, answered on the host as align_db_impl answers it
+    std::vector<int> work;
+    for (int p = 0; p < npairs; ++p)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        if (R > 0 && C > 0)
+        {
+            work.push_back(p);
+            continue;
+        }
+        const int64_t k = R + C;
+        if (!local && k > 0)
+        {
+            res[(size_t)p].score = (int32_t)(gapo + (k - 1) * gape);
+            res[(size_t)p].i_end = R;
+            res[(size_t)p].j_end = C;
+            cig[(size_t)p] = std::to_string(k) + (R > 0 ? 'I' : 'D');
+        }
+        inf.host_pairs += 1;
+    }
+    if (!work.empty())
+    {
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        const long long smax = subst_absmax(sub.data(), substsz);
+        // the pairs the 4 v + tag form holds (align_pair_impl's bound) are scored together; the others alone
+        std::vector<int> sel, alone;
+        std::vector<gsa_pair_dev> selPairs;
+        for (int p : work)
+        {
+            const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+            bool stripOk = false;
+            const int s = score_ranges(R, C, smax, gapo, gape, local, &stripOk);
+            if (s != GSA_SUCCESS) return s;
+            const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+            if (valOk && stripOk)
+            {
+                sel.push_back(p);
+                selPairs.push_back(pairs[p]);
+            }
+            else
+                alone.push_back(p);
+        }
+        const KeepLaunchRecord keep(ctx);
+        BatchScoreRoute route;
+        std::vector<gsa_score_result> sres(sel.size());
+        if (!sel.empty())
+        {
+            const int s = score_batch_impl(ctx, (int32_t)sel.size(), selPairs.data(), subst, substsz, gapo, gape, local,
+                                           sres.data(), &inf.score_ms, st, &route);
+            if (s != GSA_SUCCESS) return s;
+        }
+        const int K = route.K;
+        const int KR = K * gsa::kSparseNS;
+        const int64_t TR = 64 * (int64_t)KR;
+        // the batch pairs: scored by the launch, a positive score, and one strip within the limit
+        struct Bp
+        {
+            int p, k;  // index into pairs, into sel
+            int64_t iEnd, jEnd, movOff;
+        };
+        std::vector<Bp> bp;
+        int64_t movTotal = 0;
+        for (size_t k = 0; k < sel.size(); ++k)
+        {
+            const int p = sel[k];
+            if (!route.inBatch[k] || !(K == 2 || K == 4))
+            {
+                alone.push_back(p);
+                continue;
+            }
+            inf.strip_rows = (int32_t)TR;
+            gsa_align_db_result& r = res[(size_t)p];
+            r.score = sres[k].score;
+            r.i_end = sres[k].i_end;
+            r.j_end = sres[k].j_end;
+            r.status = 1;
+            if (local && r.score == 0)
+            {
+                r.status = 0;  // no positive cell: (0, 0), an empty CIGAR
+                inf.host_pairs += 1;
+                continue;
+            }
+            if (r.i_end < 1 || r.j_end < 1 || gsa::pair_strip_bytes(TR, r.j_end) > limit) continue;
+            bp.push_back(Bp {p, (int)k, r.i_end, r.j_end, movTotal});
+            movTotal += r.i_end + r.j_end;
+        }
+        if (!bp.empty())
+        {
+            const size_t nb = bp.size();
+            inf.batch_pairs = (int32_t)nb;
+            int sr;
+            if ((sr = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
+                (sr = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(gsa::PairWalkRec), 4096)) != GSA_SUCCESS)
+                return sr;
+            for (hipEvent_t& ev : ctx->adbev)
+                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+            gsa::PairWalkRec* const drec = ctx->buf[kBufPairBatchRec].as<gsa::PairWalkRec>();
+            unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
+            const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+            std::vector<gsa::PairWalkRec> rec(nb);
+            std::memset(rec.data(), 0, nb * sizeof(gsa::PairWalkRec));
+            std::vector<gsa::BatchPairState> state(nb);
+            for (size_t b = 0; b < nb; ++b)
+            {
+                rec[b].i = (int)bp[b].iEnd;
+                rec[b].j = (int)bp[b].jEnd;
+                rec[b].state = 4u;
+                state[b].tHi = gsa::pair_strips(TR, bp[b].iEnd) - 1;
+                state[b].J = bp[b].jEnd;
+                inf.strips += (int32_t)(state[b].tHi + 1);
+            }
+            if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(gsa::PairWalkRec), hipMemcpyHostToDevice, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            std::vector<gsa::BatchChunk> chunks;
+            std::vector<gsa::PairBatchTask> tasks;
+            std::vector<gsa::PairBatchDesc> descs;
+            std::vector<gsa::PairBatchWalk> walks;
+            std::vector<char> blob;
+            for (;;)
+            {
+                const long long used = gsa::batch_plan_round(TR, limit, state, &chunks);
+                if (chunks.empty())
+                {
+                    for (const gsa::BatchPairState& s : state)
+                        if (s.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
+                    break;
+                }
+                int s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096);
+                if (s != GSA_SUCCESS) return s;
+                unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
+                tasks.clear();
+                descs.clear();
+                walks.clear();
+                for (size_t c = 0; c < chunks.size(); ++c)
+                {
+                    const gsa::BatchChunk& ch = chunks[c];
+                    const Bp& B = bp[(size_t)ch.pair];
+                    const gsa_pair_dev& P = pairs[B.p];
+                    gsa::PairBatchDesc d;
+                    std::memset(&d, 0, sizeof(d));
+                    d.seqY = P.seqY;
+                    d.seqX = P.seqX;
+                    d.R = P.adjrows - 1;
+                    d.iEnd = (int)B.iEnd;
+                    d.J = (int)ch.c.J;
+                    d.granBase = route.granOff[(size_t)B.k];
+                    d.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
+                    d.stripBytes = ch.c.stripBytes;
+                    descs.push_back(d);
+                    for (long long t = ch.c.tLo; t <= ch.c.tHi; ++t)
+                    {
+                        gsa::PairBatchTask k;
+                        k.pair = (int)c;
+                        k.strip = (int)t;
+                        k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, t);
+                        tasks.push_back(k);
+                    }
+                    gsa::PairBatchWalk w;
+                    std::memset(&w, 0, sizeof(w));
+                    w.seqY = P.seqY;
+                    w.seqX = P.seqX;
+                    w.codes = dcodes + ch.codeOff;
+                    w.stripBytes = ch.c.stripBytes;
+                    w.tLo = (int)ch.c.tLo;
+                    w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
+                    w.rec = ch.pair;
+                    w.moves = dmoves + B.movOff;
+                    walks.push_back(w);
+                }
+                // the longest chains first
+                std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
+                    return descs[(size_t)a.pair].J > descs[(size_t)b.pair].J;
+                });
+                // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
+                const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
+                             oWalk = oDesc + descs.size() * sizeof(gsa::PairBatchDesc),
+                             tabBytes = oWalk + walks.size() * sizeof(gsa::PairBatchWalk);
+                if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
+                char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
+                blob.assign(tabBytes, 0);
+                std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
+                std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(gsa::PairBatchDesc));
+                std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(gsa::PairBatchWalk));
+                if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                gsa::PairBatchFillArgs f;
+                std::memset(&f, 0, sizeof(f));
+                f.pairs = (const gsa::PairBatchDesc*)(dtab + oDesc);
+                f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
+                f.ntasks = (int)tasks.size();
+                f.subst = subst;
+                f.substsz = substsz;
+                f.go = gapo;
+                f.ge = gape;
+                f.gran = dgran;
+                f.gran2 = dgran + route.granTotal;
+                f.codes = dcodes;
+                f.counter = (unsigned*)dtab;
+                gsa::PairBatchWalkArgs w;
+                std::memset(&w, 0, sizeof(w));
+                w.walks = (const gsa::PairBatchWalk*)(dtab + oWalk);
+                w.nwalks = (int)walks.size();
+                w.krShift = KR == 8 ? 3 : 4;
+                w.local = local ? 1 : 0;
+                w.recs = drec;
+                int grid = 1;
+                const int walkGrid = max_workgroups > 0 ? std::min(w.nwalks, (int)max_workgroups) : w.nwalks;
+                if ((e = gsa::pair_batch_fill_grid(w.local, gapo != gape, KR, f.ntasks, max_workgroups, &grid)) != hipSuccess ||
+                    (e = gsa::launch_pair_batch_trace(f, w.local, w, KR, grid, walkGrid, ctx->adbev, st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                note_launch(ctx);
+                if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(gsa::PairWalkRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                    (e = hipStreamSynchronize(st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                float m0 = 0.f, m1 = 0.f;
+                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+                inf.fill_ms += m0;
+                inf.walk_ms += m1;
+                inf.rounds += 1;
+                inf.strips_filled += (int32_t)tasks.size();
+                inf.code_bytes = std::max<int64_t>(inf.code_bytes, used);
+                // every record that came back: in range, and done or on its chunk's upper boundary
+                for (const gsa::BatchChunk& ch : chunks)
+                {
+                    const Bp& B = bp[(size_t)ch.pair];
+                    const gsa::PairWalkRec& r = rec[(size_t)ch.pair];
+                    gsa::BatchPairState& S = state[(size_t)ch.pair];
+                    if (r.n < 0 || r.n > B.iEnd + B.jEnd || r.i < 0 || r.i > B.iEnd || r.j < 0 || r.j > ch.c.J)
+                        return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                    if (r.done)
+                    {
+                        S.tHi = -1;
+                        continue;
+                    }
+                    if (ch.c.tLo < 1 || r.i != gsa::pair_chunk_stop_row(TR, ch.c) || r.j < 1)
+                        return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                    S.tHi = ch.c.tLo - 1;
+                    S.J = r.j;
+                }
+            }
+            std::vector<unsigned char> mv((size_t)movTotal + 1);
+            if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            for (size_t b = 0; b < nb; ++b)
+            {
+                gsa_align_db_result& r = res[(size_t)bp[b].p];
+                cig[(size_t)bp[b].p] = fold_cigar(mv.data() + bp[b].movOff, rec[b].n);
+                r.i_start = rec[b].i;
+                r.j_start = rec[b].j;
+                r.status = 0;
+            }
+        }
+        // the pairs that went alone, after the rounds: this overwrites kBufGran and the kBufPair* slots
+        std::sort(alone.begin(), alone.end());
+        inf.alone_pairs = (int32_t)alone.size();
+        for (int p : alone)
+        {
+            const int64_t cap = 2 * ((int64_t)pairs[p].adjrows + (int64_t)pairs[p].adjcols) + 1;
+            std::vector<char> buf((size_t)cap);
+            float ms = 0.f;
+            const int s = align_pair_impl(ctx, pairs[p].seqY, pairs[p].adjrows, pairs[p].seqX, pairs[p].adjcols, subst, substsz,
+                                          gapo, gape, local, scratch_limit, &res[(size_t)p], buf.data(), cap, nullptr, nullptr,
+                                          &ms, st);
+            if (s != GSA_SUCCESS) return s;
+            other_ms += ms;
+            if (res[(size_t)p].status == 0) cig[(size_t)p].assign(buf.data(), (size_t)res[(size_t)p].cigar_len);
+            res[(size_t)p].cigar_off = res[(size_t)p].cigar_len = 0;
+        }
+    }
+    // the strings back to back in pair order; a pair's offset does not depend on the buffer's size
+    int64_t at = 0;
+    for (int p = 0; p < npairs; ++p)
+    {
+        gsa_align_db_result& r = res[(size_t)p];
+        const int64_t len = (int64_t)cig[(size_t)p].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+        out[p] = r;
+    }
+    if (cigar_need) *cigar_need = at;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms + other_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2163,6 +2530,16 @@ int gsa_align_pair_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return align_pair_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, local, scratch_limit, out, cigar,
                            cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                        int32_t gapo, int32_t gape, int32_t local, int32_t max_workgroups, int64_t scratch_limit,
+                        gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                        gsa_align_batch_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, local, max_workgroups, scratch_limit, out, cigar,
+                            cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
 }
 
 int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,

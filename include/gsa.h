@@ -534,6 +534,63 @@ int gsa_align_pair_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const
                        int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
                        int64_t* cigar_need, gsa_align_pair_info* info, float* kernel_ms, void* stream);
 
+/* The alignments of a batch of long pairs in one call. */
+typedef struct gsa_align_batch_info {  /* what the call ran; optional out-parameter */
+    int32_t batch_pairs;    /* pairs traced by the batched route */
+    int32_t alone_pairs;    /* pairs passed on to gsa_align_pair_dev's path, one by one */
+    int32_t host_pairs;     /* pairs answered on the host: an empty side, a local score of 0 */
+    int32_t strip_rows;     /* TR: rows of a strip, the batched score kernel's ticket (1024; 512 with
+                               GSA_SCORE_K=2); 0: that kernel did not run */
+    int32_t strips;         /* strips that hold the rows 1 ... i_end, over all batch pairs */
+    int32_t strips_filled;  /* strips filled with move codes, over all rounds */
+    int32_t rounds;         /* fill + walk launch pairs */
+    int32_t pad0;
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    float score_ms, fill_ms, walk_ms; /* hipEvent time of the batched score launch, and of the fill and the walk
+                                         launches summed over the rounds (the pairs that went alone: kernel_ms only) */
+    int32_t pad1;
+} gsa_align_batch_info;
+
+/* The alignments of npairs pairs, each of any length the K-rows score kernel takes, traced on the
+ * device together.  pairs is a HOST array as gsa_score_batch_dev takes it; only seqY, adjrows, seqX and
+ * adjcols are read.  subst, substsz, gapo, gape, local: as gsa_score_batch_dev takes them.  out is a
+ * host array of npairs results.  Synchronous.
+ * Semantics: out[p] is, field for field, what gsa_align_pair_dev returns for pair p alone -- score,
+ * both cells and the CIGAR, the same recurrences and tie rule -- whatever the strip height, the round,
+ * the pair's neighbours in the batch and max_workgroups.  The CIGAR buffer follows gsa_align_db_dev's
+ * rules: the strings back to back in pair order, NUL-terminated, a pair's offset independent of
+ * cigar_cap, status 2 for a string that does not fit, *cigar_need (may be null) the bytes all need.
+ * How: gsa_score_batch_dev's launch scores every pair in one direction and leaves, per pair, the
+ * bottom row of each ticket of TR rows in the pair's own hand-off rows.  TR is 1024 in every mode
+ * (512 with GSA_SCORE_K=2), where gsa_align_pair_dev uses 512 in three of the four modes.  With those
+ * rows exact every strip of every pair is independent, so the strips of many pairs are filled with
+ * 4-bit move codes in one launch, one wave per strip, and the pairs' walks run side by side, one wave
+ * per pair (nw_pair_trace_batch.hip).  scratch_limit is the bytes of codes the call may hold at once;
+ * 0 is the default, 8 GiB.  When the strips do not all fit the call runs rounds: the pairs are taken
+ * by remaining code bytes descending, each gets its lowest unfilled strip and as many above it as
+ * still fit the round, for the columns up to where its walk stands; a pair for which nothing is left
+ * waits.  A round is one fill launch, one walk launch and one small copy back.  max_workgroups caps
+ * the grid of the fill and of the walk (0: all resident), as in gsa_align_db_multi_dev.  The scratch
+ * is counted in the peaks of gsa_mem_stats.
+ * Status 0 answered on the host: a pair with an empty side (as gsa_align_db_dev answers it), a local
+ * pair whose score is 0 (cells 0, 0, empty CIGAR).
+ * Status 1 -- score and end cell, no CIGAR -- under gsa_align_pair_dev's conditions, per pair: a value
+ * bound (largest |table value| x the shorter length + |gapo| + (R + C) |gape|) of 2^26 or more, a pair
+ * the K-rows score kernel does not take or flags, a pair whose single strip, of this call's TR rows
+ * over its columns 1 ... j_end, exceeds scratch_limit.  The strip height being 1024 here and 512 there
+ * in three modes, the last condition can differ between the two calls at a limit between the two
+ * strip sizes, and nowhere else.  The pairs the batched score launch did not run or flagged go through
+ * gsa_align_pair_dev's path one by one afterwards.  No score depends on the route.
+ * Everything gsa_score_batch_dev rejects, a negative scratch_limit, cigar_cap or max_workgroups, a null
+ * out, a null cigar with cigar_cap > 0 or a null context is errorInvalidValue before anything is
+ * enqueued.  *info (may be null) says what the call ran.  This call adds no launch kind and no knob:
+ * the record of gsa_last_launch is left untouched.  *kernel_ms (may be null) gets the hipEvent time of
+ * all kernels of the call. */
+int gsa_align_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                        int32_t substsz, int32_t gapo, int32_t gape, int32_t local, int32_t max_workgroups,
+                        int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                        int64_t* cigar_need, gsa_align_batch_info* info, float* kernel_ms, void* stream);
+
 /* Many queries against one database in one call. */
 typedef struct gsa_db_hit { int32_t subject, score, i_end, j_end; } gsa_db_hit;
 
