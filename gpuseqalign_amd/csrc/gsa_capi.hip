@@ -238,7 +238,11 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
     // the K-rows fill's int8 column profile (its instance declines a table outside int8 and the int16
     // one runs instead) wherever its LDS fits; GSA_KROW_Q8=0 keeps the int16 profile
     if (krow && env_int(ctx, "GSA_KROW_Q8", 1) != 0)
-        a.q8 = gsa::krow_lds_bytes(krowNS, krowNS == 2 ? 512 : 1024, substsz, true) <= (size_t)ctx->lds_max ? 1 : 0;
+    {
+        const size_t lds8 = fused ? gsa::full_fused_lds_bytes(krowNS, substsz, true, fused->staged)
+                                  : gsa::krow_lds_bytes(krowNS, krowNS == 2 ? 512 : 1024, substsz, true);
+        a.q8 = lds8 <= (size_t)ctx->lds_max ? 1 : 0;
+    }
     a.q8flag = ctx->ctl + 2;
     const int fullRows = gsa::kLaneRows * a.ns;  // rows per ticket of a full fill
     if (mode == gsa::kModeSparse)
@@ -248,7 +252,7 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
         a.tBy = gsa::kSparseTileBy;
     }
     std::vector<gsa::PairDesc> hd((size_t)npairs);
-    long long tickets = 0, gran = 0, maxWork = 1;
+    long long tickets = 0, gran = 0, maxWork = 1, span = 1;
     for (int p = 0; p < npairs; ++p)
     {
         const gsa_pair_dev& in = pairs[p];
@@ -291,6 +295,14 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
             }
             maxWork = std::max<long long>(maxWork, std::max((long long)d.tcols * (tileBx + 1),
                                                             (long long)d.trows * (gsa::kSparseTileBy + 1)));
+            // the largest min(i, j) over the cells an output word depends on (StripArgs::qcap): header rows
+            // end at row (trows - 1) tBy and run to column Cp, header columns end at column (tcols - 1) tBx
+            // and run to row trows tBy; pass 1 of a full fill is read inside the matrix only.  Cells past
+            // both may wrap: nothing reads them.
+            const long long tBy = gsa::kSparseTileBy;
+            span = std::max(span, rows64 ? (long long)std::min(d.R, d.C)
+                                         : std::max(std::min<long long>((d.trows - 1) * tBy, d.Cp),
+                                                    std::min<long long>(d.trows * tBy, (long long)(d.tcols - 1) * tileBx)));
         }
         d.ticketBase = (int)tickets;
         d.granOff = gran;
@@ -308,6 +320,7 @@ int enqueue_batch(gsa_ctx* ctx, int mode, int npairs, const gsa_pair_dev* pairs,
     a.nPairs = npairs;
     a.nTicketsTotal = (int)tickets;
     a.sched = sched.empty() ? nullptr : (const int*)(ddesc + npairs);
+    a.qcap = (int)(0x7fffffffll / span);
     e = gsa::launch_headers(a, mode, maxWork, st);
     if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     // gsa_last_launch: the instance decided above (a two-pass full fill's caller then names the kind)
@@ -692,8 +705,11 @@ int enqueue_full_twopass(gsa_ctx* ctx, int npairs, const gsa_pair_dev* pairs, co
     // them); a small one's keeps HBM idle enough for the strips to store it directly, without the
     // staging's ~5 % per step (nw_krow.hip nw_full_fused_kernel): 10k direct, 100k staged
     const int stagedKnob = env_int(ctx, "GSA_FUSED_STAGED", -1);  // (tests: both instances at every size)
-    const bool staged = stagedKnob >= 0 ? stagedKnob != 0
-                                        : (long long)(pairs[0].adjrows - 1) * (long long)(pairs[0].adjcols - 1) > (1ll << 30);
+    // (the staging's 32 KiB beside pass 1's profile: a table of more than 26 letters leaves no room for
+    // it in LDS, and the strips store directly at every size)
+    const bool staged = (stagedKnob >= 0 ? stagedKnob != 0
+                                         : (long long)(pairs[0].adjrows - 1) * (long long)(pairs[0].adjcols - 1) > (1ll << 30)) &&
+                        gsa::full_fused_lds_bytes(ns, substsz, false, true) <= (size_t)ctx->lds_max;
     const FusedLaunch fl {&xa, ns, gsa::kExpStreamWaves, 1 << 30, staged};
     const int xGrid = (int)std::max<long long>(1, std::min<long long>(ctx->cu_count, (nEntries + xRun - 1) / xRun));
     // gsa_set_full_timing: events before pass 1, between the passes and after pass 2, and the

@@ -286,6 +286,9 @@ inline void lap(gsa_ctx* ctx, const char* name)
 inline int fail(gsa_ctx* ctx, hipError_t e, int stat)
 {
     ctx->last_hip_error = (int)e;
+    // the runtime keeps its own last error until it is read: left there, the next call's launch check
+    // (hipGetLastError behind its first kernel) would report this call's failure
+    (void)hipGetLastError();
     return stat;
 }
 

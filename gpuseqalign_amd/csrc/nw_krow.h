@@ -28,7 +28,8 @@ __host__ __device__ constexpr int krow_tickets(int trows, int ns, int k)
 size_t krow_lds_bytes(int ns, int lw, int substsz, bool q8 = false);
 // StripArgs / PairDesc / granule contract as launch_strip_fill (sparse mode, a.tBx, a.tBy,
 // per-pair hrow/hcol/trows/tcols/Cp); tickets of a pair = krow_tickets(trows, ns, k).
-// Every |s - 2g| must fit int16 (the kernel sets error bit 2 otherwise).  grid <= 0: every resident slot.
+// Every s - 2g must lie in [-32768, 32767] and be at most a.qcap (the kernel sets error bit 2 otherwise).
+// grid <= 0: every resident slot.
 // The profile ring holds 512 columns for ns = 2, 1024 otherwise (lw is reserved).
 hipError_t launch_krow_fill(const StripArgs& a, int ns, int k, int lw, int grid, hipStream_t stream);
 // Pass 1 of the two-pass full fill (nw_expand.h): the sparse fill (K = 4, ns = 4 or 8, a.tBx =
@@ -40,6 +41,9 @@ hipError_t launch_krow_fill_xr(const StripArgs& a, int ns, int grid, hipStream_t
 // words a.xdone of the strips whose rows and header column it reads.  (ns, waves): (4, 8) or
 // (8, 12).  grid <= 0: every resident slot.
 // staged: the strips hand row 64m to a storer wave (large pairs); else they store it themselves
+// full_fused_lds_bytes: the workgroup's dynamic LDS (pass 1's K-rows layout plus the staging, or the
+// expansion's if larger); the caller picks q8 and staged so that it fits the device
+size_t full_fused_lds_bytes(int ns, int substsz, bool q8, bool staged);
 hipError_t launch_full_fused(const StripArgs& a, int ns, int waves, bool staged, int grid, hipStream_t stream);
 
 // Score-only NW / SW (modes kModeScoreAG/AGL/SW/SWL of nw_strip.h, same StripArgs contract as

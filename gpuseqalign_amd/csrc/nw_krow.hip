@@ -27,6 +27,9 @@
 // one column, dword d of copy p holding columns (2d-p, 2d-p+1), so every lane reads its 16 columns
 // of a block as 8 aligned dwords at base + immediate offsets (copy = lane parity): no VALU
 // addressing, 8*K/2 ds_read2 per block; the halves are taken by SDWA operands of the adds.
+// Value range (include/gsa.h): every q in [-32768, 32767] ([-128, 127]: the int8 profile), and, since
+// 0 <= H'(i, j) <= max(q, 0) min(i, j) in int32, every q <= StripArgs::qcap; the kernel's prologue tests
+// both once per workgroup and sets error bit 2 otherwise.
 //
 // Sparse output.  Header rows (the last row of a tile row) are the last row of a ticket: the
 // drain wave writes them with the granules.  Header columns are captured by the strips: in a
@@ -1442,8 +1445,9 @@ __global__ void __launch_bounds__((64 * kr_waves<NS, PT>()), 1) nw_krow_kernel(S
     {
         const int x = k / kSubRow, yy = k % kSubRow;
         const int v = yy < a.substsz ? G(a.subst)[yy * a.substsz + x] - 2 * a.g : 0;
-        bad |= v < -32768 || v > 32767;  // the profile holds int16
-        bad8 |= v < -128 || v > 127;      // ... or int8
+        // the profile holds int16 and H' <= max(q, 0) min(i, j) stays in int32 (StripArgs::qcap)
+        bad |= v < -32768 || v > 32767 || v > a.qcap;
+        bad8 |= v < -128 || v > 127 || v > a.qcap;  // ... or int8; past qcap the int16 instance reports
         lds_st(L.sub + 4u * k, v);
     }
     if constexpr (Q8)
@@ -2527,8 +2531,8 @@ __global__ void __launch_bounds__(64 * W) nw_full_fused_kernel(StripArgs a)
     {
         const int x = k / kSubRow, yy = k % kSubRow;
         const int v = yy < a.substsz ? G(a.subst)[yy * a.substsz + x] - 2 * a.g : 0;
-        bad |= v < -32768 || v > 32767;
-        bad8 |= v < -128 || v > 127;
+        bad |= v < -32768 || v > 32767 || v > a.qcap;  // (nw_krow_kernel)
+        bad8 |= v < -128 || v > 127 || v > a.qcap;
         lds_st(L.sub + 4u * k, v);
     }
     if constexpr (Q8)
@@ -2652,8 +2656,7 @@ hipError_t launch_fused1(const StripArgs& a, int grid, hipStream_t stream, bool 
 {
     static_assert(W == kExpStreamWaves, "the streamed expansion's workgroup");
     static_assert(kr_waves<NS>() < W, "a storer wave beside the pass-1 roles");
-    const size_t lds = std::max(krow_lds_bytes(NS, 1024, a.substsz, Q8) + (PTF == 3 ? kr_xstage_bytes(NS) : 0u),
-                                expand_stream_lds_bytes(a.substsz));
+    const size_t lds = full_fused_lds_bytes(NS, a.substsz, Q8, PTF == 3);
     auto kern = nw_full_fused_kernel<NS, W, Q8, PTF>;
     constexpr int kThreads = 64 * W;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -2684,6 +2687,11 @@ hipError_t launch_fused(const StripArgs& a, int grid, hipStream_t stream)
 }
 
 }  // namespace
+
+size_t full_fused_lds_bytes(int ns, int substsz, bool q8, bool staged)
+{
+    return std::max(krow_lds_bytes(ns, 1024, substsz, q8) + (staged ? kr_xstage_bytes(ns) : 0u), expand_stream_lds_bytes(substsz));
+}
 
 hipError_t launch_full_fused(const StripArgs& a, int ns, int waves, bool staged, int grid, hipStream_t stream)
 {

@@ -143,6 +143,13 @@ struct StripArgs
     // score_bidi, local, the way back: a one-pair launch that starts at the pair's ticket tkFirst,
     // its row above in that ticket's predecessor's granules (copied there with this epoch)
     int tkFirst;
+    // Sparse fills and pass 1 of the full fills (K-rows and strip kernels; enqueue_batch sets it): the
+    // largest q = s - 2g whose shifted accumulator stays in int32.  H' = H - (i+j) g is 0 on the borders,
+    // a gap step adds 0 and a diagonal step q, so 0 <= H'(i, j) <= max(q, 0) min(i, j).  qcap =
+    // floor((2^31 - 1) / m), m the largest min(i, j) over the cells an output word depends on, over all
+    // pairs of the launch (include/gsa.h).  A table with a larger q sets error bit 2, as one outside
+    // int16 does.
+    int qcap;
 };
 // Score batch (nw_krow.hip nw_kscore_kernel: sched set, or nPairs > 1 without bidiTop): swBest is
 // the base of two result words per pair, pair p's at swBest[2p] (NW: the result cell in the low

@@ -218,6 +218,9 @@ __device__ __forceinline__ void strip_wave(const StripArgs& a, const Lds& L, int
                 // LG: s - 2g;  AG (H' = H - (i+j)ge, diagonal carried as Hgo' = H' + d): s - 2ge - d
                 v[k] = srow[k][x] - (is_score_mode(MODE) ? a.ge + a.go : 2 * g);
                 bad |= (v[k] < -32767) || (v[k] > 32767);
+                // the sparse fill's H' <= max(q, 0) min(i, j) stays in int32 (StripArgs::qcap; the score
+                // modes' spans are bounded on the host)
+                if (MODE == kModeSparse) bad |= v[k] > a.qcap;
             }
             int2v p;
             p.x = (v[0] & 0xffff) | (v[1] << 16);

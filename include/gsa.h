@@ -102,7 +102,25 @@ int gsa_sparse_geometry(int32_t adjrows, int32_t adjcols, int32_t tileBx, gsa_sp
  * is STICKY: a time-out in any launch enqueued since the last gsa_sync() makes that gsa_sync()
  * return GSA_ERROR_KERNEL_FAILURE (launches enqueued behind the failed one give up at once), and
  * gsa_sync() then clears it, so the context is usable again.  One stream per context at a time
- * (the launches share the context's ticket word). */
+ * (the launches share the context's ticket word).
+ * Accepted value range, the same for every fill entry point (gsa_fill_*_dev, their pitched and batch
+ * forms, gsa_align_full, gsa_align_sparse, gsa_align_sparse_pt).  gapo may have any sign; substsz is
+ * 1 .. 32, else errorInvalidValue before anything is enqueued.  The fill kernels keep
+ * H' = H - (i + j) gapo, which is 0 on the borders and grows by q = s - 2 gapo on a diagonal step and
+ * by 0 on a gap step, so 0 <= H'(i, j) <= qmax min(i, j) with qmax the largest q of the table (at
+ * least 0).  With m the largest min(i, j) over the cells an output word depends on --
+ *   sparse: max(min((trows - 1) tileBy, tcols tileBx), min(trows tileBy, (tcols - 1) tileBx)), the
+ *           header rows' and the header columns' far corners in the padded matrix;
+ *   full:   min(adjrows - 1, adjcols - 1);
+ *   batch:  the largest m of its pairs --
+ * a fill needs every q in [-32768, 32767] (the strip kernel, GSA_SPARSE_KERNEL=strip: [-32767, 32767])
+ * and qmax m < 2^31.  The table is device memory, so the kernels test it, once per workgroup: a table
+ * outside sets bit 2 of the error word before any ticket is taken, no output word is valid, and the
+ * next gsa_sync() (or the host-buffer entry point itself) returns GSA_ERROR_KERNEL_FAILURE and clears
+ * the word; in a batch one pair past the bound refuses the whole call.  Inside the range every word
+ * is exact, on whichever instance runs (a table with some q outside [-128, 127] runs on the int16
+ * instance, gsa_launch_info::q8_declined).  The one-pass lane fill (GSA_FULL_KERNEL=lane) keeps H
+ * itself and takes every table whose H fits int32.  Nothing checks that H itself fits int32. */
 int gsa_fill_full_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t* score, void* stream);
 int gsa_fill_sparse_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,

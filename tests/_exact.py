@@ -14,7 +14,11 @@ the first one holding it in row-major order, (0, 0) for a score of 0.
 Sequences carry their header element in front, as every entry point takes them: R = len(Y) - 1.
 
 The sweep goes by anti-diagonals d = i + j, every array indexed by the row i: the three cells a cell
-reads are on the diagonals d - 1 (rows i and i - 1) and d - 2 (row i - 1)."""
+reads are on the diagonals d - 1 (rows i and i - 1) and d - 2 (row i - 1).
+
+The NW-LG fill family (fill_lg, headers_lg, homopolymer_lg) has its own reference further down: the
+whole matrix of the one-gap-cost recurrence, its tile headers, and a closed form for pairs too long
+to fill."""
 import re
 
 import numpy as np
@@ -75,6 +79,84 @@ def score(Y, X, sub, go, ge, local):
     if local:
         return best, bi, bj
     return int(h1[R]), R, C
+
+
+def fill_lg(Y, X, sub, g):
+    """The (R + 1) x (C + 1) int64 matrix of the NW-LG fill, from the recurrence include/gsa.h states
+    (UpdateScore): H[0][j] = j g, H[i][0] = i g, H[i][j] = max(H[i-1][j-1] + s(Y[i], X[j]),
+    H[i-1][j] + g, H[i][j-1] + g), s = sub[Y letter][X letter], for g of any sign.
+    A row at a time: with t[j] the best of the two moves out of row i - 1 (t[0] = i g), H[i][j] is the
+    largest t[k] + (j - k) g over k <= j, a running maximum of t[k] - k g."""
+    Y, X, S = np.asarray(Y, dtype=np.int64), np.asarray(X, dtype=np.int64), _table(sub)
+    R, C, g = len(Y) - 1, len(X) - 1, int(g)
+    jg = np.arange(C + 1, dtype=np.int64) * g
+    H = np.empty((R + 1, C + 1), np.int64)
+    H[0] = jg
+    t = np.empty(C + 1, np.int64)
+    for i in range(1, R + 1):
+        up = H[i - 1]
+        t[0] = i * g
+        np.maximum(up[:-1] + S[Y[i], X[1:]], up[1:] + g, out=t[1:])
+        H[i] = np.maximum.accumulate(t - jg) + jg
+    return H
+
+
+def pad_to_tiles(Y, X, tBy, tBx):
+    """Both sequences padded with letter 0 to whole tiles (at least one): the pair whose matrix the
+    sparse representation samples."""
+    Y, X = np.asarray(Y, dtype=np.int64), np.asarray(X, dtype=np.int64)
+    trows, tcols = max(1, -(-(len(Y) - 1) // tBy)), max(1, -(-(len(X) - 1) // tBx))
+    Yp, Xp = np.zeros(trows * tBy + 1, np.int64), np.zeros(tcols * tBx + 1, np.int64)
+    Yp[:len(Y)], Xp[:len(X)] = Y, X
+    return Yp, Xp, trows, tcols
+
+
+def headers_of(H, trows, tcols, tBy, tBx):
+    """(tileHrowMat, tileHcolMat) of include/gsa.h out of the padded pair's matrix H: tile-major,
+    k = tcols iT + jT, 1 + tBx resp. 1 + tBy values per tile, element 0 the tile's corner:
+    hrow[k][e] = H[iT tBy][jT tBx + e], hcol[k][e] = H[iT tBy + e][jT tBx]."""
+    rows = H[np.arange(trows) * tBy]                                      # trows x (Cp + 1)
+    hrow = rows[:, np.arange(tcols)[:, None] * tBx + np.arange(tBx + 1)]  # trows x tcols x (1 + tBx)
+    cols = H[:, np.arange(tcols) * tBx]                                   # (Rp + 1) x tcols
+    hcol = cols[np.arange(trows)[:, None] * tBy + np.arange(tBy + 1)]     # trows x (1 + tBy) x tcols
+    return hrow.reshape(-1), hcol.transpose(0, 2, 1).reshape(-1)
+
+
+def headers_lg(Y, X, sub, g, tBy, tBx):
+    """(tileHrowMat, tileHcolMat), int64, from fill_lg of the pair padded with letter 0."""
+    Yp, Xp, trows, tcols = pad_to_tiles(Y, X, tBy, tBx)
+    return headers_of(fill_lg(Yp, Xp, sub, g), trows, tcols, tBy, tBx)
+
+
+class homopolymer_lg:
+    """The fill of two runs of letter 0, R and C letters, with s(0, 0) = v >= 0 and g <= 0, in closed
+    form: H[i][j] = v min(i, j) + g |i - j| (the diagonal as far as it goes, then one gap; no path does
+    better since a diagonal step gains v >= 0 >= 2 g over two gap steps).  The padding letter is 0 too,
+    so the form holds over the padded region.  Only rows, columns and headers are ever built."""
+
+    def __init__(self, R, C, v, g):
+        assert v >= 0 and g <= 0, (v, g)
+        self.R, self.C, self.v, self.g = int(R), int(C), int(v), int(g)
+
+    def at(self, i, j):
+        """H at the (broadcast) int64 indices i, j."""
+        i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+        return self.v * np.minimum(i, j) + self.g * np.abs(i - j)
+
+    def cost(self):
+        return int(self.at(self.R, self.C))
+
+    def rows(self, i0, i1):
+        """Rows i0 .. i1 - 1 of the unpadded matrix, (i1 - i0) x (C + 1)."""
+        return self.at(np.arange(i0, i1)[:, None], np.arange(self.C + 1)[None, :])
+
+    def headers(self, tBy, tBx):
+        """(tileHrowMat, tileHcolMat), int64, laid out as headers_of lays them out."""
+        trows, tcols = max(1, -(-self.R // tBy)), max(1, -(-self.C // tBx))
+        iT, jT = np.arange(trows)[:, None, None], np.arange(tcols)[None, :, None]
+        hrow = self.at(iT * tBy, jT * tBx + np.arange(tBx + 1)[None, None, :])
+        hcol = self.at(iT * tBy + np.arange(tBy + 1)[None, None, :], jT * tBx)
+        return hrow.reshape(-1), hcol.reshape(-1)
 
 
 def runs(cigar):
