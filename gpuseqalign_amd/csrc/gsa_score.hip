@@ -23,6 +23,8 @@
 #include "nw_lanes_semi_trace.h"
 #include "nw_lanes_trace.h"
 #include "nw_lanes_trace_multi.h"
+#include "nw_pair_semi_plan.h"
+#include "nw_pair_semi_trace.h"
 #include "nw_pair_trace.h"
 #include "nw_pair_trace_batch.h"
 #include "nw_pair_trace_batch_plan.h"
@@ -2518,9 +2520,332 @@ int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
     return GSA_SUCCESS;
 }
 
+
+// What semi_pair_score's launch ran: the K-rows geometry whose checkpoint rows stay in kBufGran (row t
+// at t gran_stride(C), the affine second array `tickets` rows behind).
+struct SemiRoute
+{
+    int K = 0;
+    int64_t tickets = 0;
+    long long pmax = 0;  // max(0, largest table value): the window's bound (nw_pair_semi_plan.h)
+};
+
+// gsa_score_semi_dev for a pair with letters on both sides: the range tests of a mode without a
+// second path, then the K-rows score kernel's semi-global instance in one direction (row R into
+// kBufBidi) and the kernel that takes that row's first maximum; one copy brings score and end column
+// back.  gsa_last_launch's record and the fills' sticky error word are left alone.
+int semi_pair_score(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX, int64_t C, const int32_t* subst,
+                    int32_t substsz, int32_t gapo, int32_t gape, bool forAlign, gsa_score_result* out, hipStream_t st,
+                    SemiRoute* route)
+{
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+    if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    const long long smax = subst_absmax(sub.data(), substsz);
+    bool stripOk = false;
+    int s = score_ranges(R, C, smax, gapo, gape, 0, &stripOk);
+    if (s != GSA_SUCCESS) return s;
+    if (!stripOk) return GSA_ERROR_INVALID_VALUE;  // span < 2^28: the shifted values' room in int32
+    if (gsa::krow_score_lds_bytes(substsz) > (size_t)ctx->lds_max) return GSA_ERROR_INVALID_VALUE;
+    // the kernel's own test of the shifted table (nw_kscore_kernel: error bit 2)
+    for (const int32_t v0 : sub)
+    {
+        const long long v = (long long)v0 - gapo - gape;
+        if (v <= -32768 || v > 32767) return GSA_ERROR_INVALID_VALUE;
+    }
+    // the fill keeps 4 x value + source (align_pair_impl's bound)
+    if (forAlign && smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= gsa::kDbTraceMaxValue)
+        return GSA_ERROR_INVALID_VALUE;
+    // rows per lane as score_ag_strip picks them for a global pair
+    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
+    const int scoreK = kenv == 2 || kenv == 4 ? kenv : (gapo == gape) ? 4 : 2;
+    const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
+    const int64_t tickets = (R + TR - 1) / TR;
+    if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+    if (route)
+    {
+        route->K = scoreK;
+        route->tickets = tickets;
+        route->pmax = std::max<long long>(0, *std::max_element(sub.begin(), sub.end()));
+    }
+    const KeepLaunchRecord keep(ctx);
+    gsa::StripArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.subst = subst;
+    a.substsz = substsz;
+    a.g = gapo;
+    a.go = gapo;
+    a.ge = gape;
+    a.ns = gsa::kSparseNS;
+    gsa::PairDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.seqY = seqY;
+    d.seqX = seqX;
+    d.R = (int)R;
+    d.C = (int)C;
+    d.Cp = (int)C;
+    d.nTickets = (int)tickets;
+    if ((s = ensure_desc(ctx, 1)) != GSA_SUCCESS) return s;
+    gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
+    if ((e = hipMemcpyAsync(ddesc, &d, sizeof(d), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    const size_t gran = (size_t)tickets * (size_t)gsa::gran_stride((int)C);
+    if ((s = ensure_gran(ctx, 2 * gran, st)) != GSA_SUCCESS) return s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
+    // row R: columns -kTapPad .. C + 79, as the tap rows
+    if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], (size_t)(gsa::kTapPad + C + 80) * sizeof(int))) != GSA_SUCCESS) return s;
+    unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+    a.pairs = ddesc;
+    a.nPairs = 1;
+    a.nTicketsTotal = (int)tickets;
+    a.gran = dgran;
+    a.gran2 = dgran + gran;
+    a.ticket = ctx->ctl;
+    a.err = (unsigned*)(sctl + 3);  // the score kernels' own error word (score_ag_strip)
+    a.spin = ctx->spin_ticks;
+    a.agResult = (int*)sctl;
+    a.swBest = sctl + 1;
+    a.idxBits = sw_idx_bits(R, C);
+    a.rowR = ctx->buf[kBufBidi].as<int>();
+    a.epoch = ++ctx->epoch;
+    if (a.epoch == 0) a.epoch = ++ctx->epoch;
+    if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    (void)hipEventRecord(ctx->ev0, st);
+    const int grid = std::max(1, std::min((int)tickets, ctx->cu_count));
+    const int mode = gapo == gape ? gsa::kModeScoreSGL : gsa::kModeScoreSG;
+    // the int8 profile as score_ag_strip picks it (GSA_KROW_Q8)
+    const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+    a.q8 = (q8env != 0 && (q8env == 2 || scoreK == 4) && gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+    a.q8flag = ctx->ctl + 2;
+    if ((e = gsa::launch_krow_score_semi(a, mode, scoreK, grid, st)) != hipSuccess ||
+        (e = gsa::launch_semi_rowmax(a.rowR, (int)R, (int)C, gapo, gape, (int*)sctl, (int*)(sctl + 1), st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    note_launch(ctx);
+    (void)hipEventRecord(ctx->ev1, st);
+    unsigned long long res[4] = {0, 0, 0, 0};
+    if ((e = hipMemcpyAsync(res, sctl, sizeof(res), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
+    if ((unsigned)res[3] != 0) return GSA_ERROR_KERNEL_FAILURE;
+    out->score = (int32_t)(uint32_t)res[0];
+    out->i_end = R;
+    out->j_end = (int64_t)(int32_t)(uint32_t)res[1];
+    if (out->j_end < 0 || out->j_end > C) return GSA_ERROR_KERNEL_FAILURE;
+    return GSA_SUCCESS;
+}
+
+int score_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                    const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    const int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    out->calc_kernel_ms = 0.f;
+    if (R == 0 || C == 0)
+    {
+        // an empty side, answered on the host as the database calls answer it
+        out->score = R == 0 ? 0 : (int32_t)(gapo + (R - 1) * gape);
+        out->i_end = R;
+        out->j_end = 0;
+        return GSA_SUCCESS;
+    }
+    return semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, false, out, st, nullptr);
+}
+
+
+// gsa_align_pair_semi_dev: score and end column from semi_pair_score, whose checkpoint rows stay in
+// kBufGran; the column window from the score (nw_pair_semi_plan.h); then, bottom-up from row R's strip
+// to strip 0, chunks of strips whose windowed move codes fit scratch_limit, a fill and a walk launch
+// per chunk and one small copy of the walk's record back (nw_pair_semi_trace.hip); at the end the
+// move bytes, folded into the CIGAR.  gsa_last_launch's record is left as it was.
+int align_pair_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                         const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
+                         gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                         gsa_align_pair_semi_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_pair_semi_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : (int64_t)gsa::kPairTraceScratch;
+    gsa_align_db_result r;
+    std::memset(&r, 0, sizeof(r));
+    std::string cig;
+    if (R == 0 || C == 0)
+    {
+        // an empty side, answered on the host as the database calls answer it
+        if (R > 0)
+        {
+            r.score = (int32_t)(gapo + (R - 1) * gape);
+            r.i_end = R;
+            cig = std::to_string(R) + 'I';
+        }
+    }
+    else
+    {
+        gsa_score_result sr {};
+        SemiRoute route;
+        if ((s = semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, true, &sr, st, &route)) != GSA_SUCCESS)
+            return s;
+        const KeepLaunchRecord keep(ctx);
+        hipError_t e = hipSuccess;
+        inf.score_ms = sr.calc_kernel_ms;
+        r.score = sr.score;
+        r.i_end = R;
+        r.j_end = sr.j_end;
+        const int KR = route.K * gsa::kSparseNS;
+        const int64_t TR = 64 * (int64_t)KR;
+        const int64_t jEnd = sr.j_end;
+        const int64_t strips = gsa::pair_strips(TR, R);
+        inf.strip_rows = (int32_t)TR;
+        inf.strips = (int32_t)strips;
+        if (jEnd == 0)
+            cig = std::to_string(R) + 'I';  // the all-insert alignment on column 0: no codes
+        else
+        {
+            const int64_t jW = gsa::semi_window(R, jEnd, sr.score, route.pmax, gape);
+            inf.j_window = jW;
+            gsa::PairChunk ch;
+            // (a limit below one strip's windowed codes: known only once the score is)
+            if (!gsa::semi_plan_chunk(TR, strips - 1, jEnd, jW, limit, &ch)) return GSA_ERROR_INVALID_VALUE;
+            if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
+                (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(R + jEnd - jW), 4096)) != GSA_SUCCESS)
+                return s;
+            for (hipEvent_t& ev : ctx->adbev)
+                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+            char* const meta = ctx->buf[kBufPairMeta].as<char>();
+            gsa::SemiWalkRec* const drec = (gsa::SemiWalkRec*)(meta + 64);
+            const size_t stride = (size_t)gsa::gran_stride((int)C);
+            gsa::SemiWalkRec rec;
+            std::memset(&rec, 0, sizeof(rec));
+            rec.i = (int)R;
+            rec.j = (int)jEnd;
+            rec.state = 4u;
+            if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            for (;;)
+            {
+                const int nstrips = (int)(ch.tHi - ch.tLo + 1);
+                const int64_t J = jW + ch.J;  // the chunk's last column
+                if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
+                if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                gsa::SemiFillArgs f;
+                std::memset(&f, 0, sizeof(f));
+                f.seqY = seqY;
+                f.seqX = seqX;
+                f.subst = subst;
+                f.substsz = substsz;
+                f.go = gapo;
+                f.ge = gape;
+                f.R = (int)R;
+                f.jW = (int)jW;
+                f.J = (int)J;
+                f.tLo = (int)ch.tLo;
+                f.nstrips = nstrips;
+                f.gran = ctx->buf[kBufGran].as<unsigned long long>();
+                f.gran2 = f.gran + (size_t)route.tickets * stride;
+                f.granStride = (long long)stride;
+                f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
+                f.stripBytes = ch.stripBytes;
+                f.counter = (unsigned*)meta;
+                gsa::SemiWalkArgs w;
+                std::memset(&w, 0, sizeof(w));
+                w.seqY = seqY;
+                w.seqX = seqX;
+                w.codes = f.codes;
+                w.stripBytes = ch.stripBytes;
+                w.krShift = KR == 8 ? 3 : 4;
+                w.tLo = (int)ch.tLo;
+                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
+                w.jW = (int)jW;
+                w.rec = drec;
+                w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+                int grid = 1;
+                if ((e = gsa::semi_fill_grid(gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
+                    (e = gsa::launch_semi_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                note_launch(ctx);
+                if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                    (e = hipStreamSynchronize(st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                float m0 = 0.f, m1 = 0.f;
+                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+                inf.fill_ms += m0;
+                inf.walk_ms += m1;
+                inf.chunks += 1;
+                inf.strips_filled += nstrips;
+                inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
+                // the walk left the window (the bound excludes it), or wrote past its moves
+                if (rec.left || rec.n < 0 || rec.n > R + jEnd - jW) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                if (rec.done) break;
+                // on the chunk's upper boundary: the next chunk, for the columns up to here
+                if (ch.tLo < 1 || rec.i != w.iStop || rec.j <= jW || rec.j > J ||
+                    !gsa::semi_plan_chunk(TR, ch.tLo - 1, rec.j, jW, limit, &ch))
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            }
+            if (rec.i != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            std::vector<unsigned char> mv((size_t)rec.n + 1);
+            if (rec.n > 0 &&
+                ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                 (e = hipStreamSynchronize(st)) != hipSuccess))
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            cig = fold_cigar(mv.data(), rec.n);
+            r.i_start = 0;
+            r.j_start = rec.j;
+        }
+    }
+    const int64_t len = (int64_t)cig.size();
+    if (len + 1 <= cigar_cap)
+    {
+        std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
+        r.cigar_len = len;
+    }
+    else
+        r.status = 2;
+    if (cigar_need) *cigar_need = len + 1;
+    *out = r;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_align_pair_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
+                            gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                            gsa_align_pair_semi_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_pair_semi_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, scratch_limit, out, cigar,
+                                cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out,
+                       void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_semi_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, out, pick_stream(ctx, stream));
+}
 
 int gsa_align_pair_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                        const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,

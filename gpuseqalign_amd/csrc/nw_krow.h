@@ -60,5 +60,13 @@ size_t krow_score_lds_bytes(int substsz, bool q8 = false);
 hipError_t launch_krow_score(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
 // (the affine modes' instances, in nw_kscore_ag.hip; called by launch_krow_score)
 hipError_t launch_krow_score_affine(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
+// Semi-global score of one pair (modes kModeScoreSG / SGL, nw_kscore_semi.hip): launch_krow_score's
+// contract for one pair in a global mode (no taps, no batch, no bidi fields, grid > 0), except that no
+// result cell is written: the strip that holds row R stores that row's shifted Hgo' at
+// a.rowR[kTapPad + column], a buffer of kTapPad + a.Cp + 80 ints.  launch_semi_rowmax, enqueued
+// behind it, unshifts the row and writes the maximum over the columns 0 .. C (column 0 analytic:
+// go + (R - 1) ge) to *score and the smallest column that attains it to *jend.
+hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
+hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream);
 
 }  // namespace gsa

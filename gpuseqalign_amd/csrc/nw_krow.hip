@@ -1592,6 +1592,7 @@ hipError_t launch_kr(const StripArgs& a, int grid, hipStream_t stream)
 // through a gap and never tie a real cell's score.
 // ====================================================================================
 constexpr int kNegS = -(1 << 29);  // "before the matrix": far from overflow, never the maximum
+typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));  // 16 B at a 4-byte boundary (row R's stores)
 constexpr int kNegQ = -32768;      // profile value of the NEG column letter
 constexpr uint32_t kRing2Off = (uint32_t)(kKrowNSDefault + 1) * kRing * 4u;  // ring2 = ring + this
 
@@ -1622,6 +1623,7 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
     constexpr int NS = kKrowNSDefault, LW = 1024;
     constexpr bool AG = !is_lin_mode(MODE);  // E' and F' carried
     constexpr bool SW = is_sw_mode(MODE);
+    constexpr bool SG = is_sg_mode(MODE);  // semi-global: row R over every column instead of the cell (R, C)
     const int Cp = a.Cp;
     const int ge = a.ge;
     const int dd = AG ? a.go - a.ge : 0;
@@ -1804,6 +1806,15 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
         tapBF = (uint64_t)(uintptr_t)a.tapF + 4ull * (uint64_t)(kTapPad - 1 - lane);
     }
     const uint64_t tapMask = 1ull << (tapLane & 63);
+    // semi-global: the lane that holds row R keeps its register row there, every other lane -1, and
+    // its own address of block 0's 16 words of that row (per-lane values: no scalar state across blocks)
+    int rsel = -1;
+    uint64_t rowB = 0;
+    if constexpr (SG)
+    {
+        rsel = (hasR && lane == laneR) ? kR : -1;
+        rowB = (uint64_t)(uintptr_t)a.rowR + 4ull * (uint64_t)(kTapPad - lane);
+    }
 
     auto block = [&](int b, int (&qc)[K][kQD], int (&qn)[K][kQD]) {
         {
@@ -1934,6 +1945,33 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
             z0 = zz[SW ? kBlk : 0];
             wv = 15u - 16u * (uint32_t)z0;
         }
+        else if constexpr (SG)
+        {
+            // row R of this block: lane laneR's va[kR][u] is the Hgo' of column 16 b + u - laneR.  That
+            // lane alone (the branch masks the others off: rsel < 0 in every other lane and in every
+            // other strip) stores the 16 words, 64 B per block, at rowR[kTapPad + column]
+            if (rsel >= 0)
+            {
+                // (a global pointer: a flat store would count in lgkmcnt and stall the strip's LDS waits.
+                // The register row by a select per value: a uniform branch on kR around four copies of
+                // the stores measured 1-6 % slower, profiles/align_pair_semi_ab.txt)
+                const gptr<int4u> dst = (gptr<int4u>)(rowB + 64ull * (uint64_t)b);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                {
+                    int4u sr;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                    {
+                        int v = va[0][4 * q + j];
+#pragma unroll
+                        for (int k = 1; k < K; ++k) v = (rsel == k) ? va[k][4 * q + j] : v;
+                        sr[j] = v;
+                    }
+                    dst[q] = sr;
+                }
+            }
+        }
         else
         {
             if (hasR && (tStar >> 4) == b)
@@ -2024,7 +2062,9 @@ __device__ __forceinline__ void ks_feed(const StripArgs& a, const KsLds& L, int 
             {
                 // row 0 shifted: global H'(0,c) = d for c >= 1 (0 at c = 0), local -c ge (H = 0);
                 // carried as Hgo' = H' + d; F' = -inf
-                v = is_sw_mode(MODE) ? dd - c * a.ge : (c == 0 ? dd : 2 * dd);
+                // (semi-global: the local row, H = 0 at every column; column 0 then comes out global,
+                // the NEG letter at columns < 1 leaving only the F chain down from H(0, 0) = 0)
+                v = (is_sw_mode(MODE) || is_sg_mode(MODE)) ? dd - c * a.ge : (c == 0 ? dd : 2 * dd);
                 good = in;
             }
             else
@@ -2445,7 +2485,62 @@ hipError_t launch_ks(const StripArgs& a, int grid, hipStream_t stream)
 
 }  // namespace
 
-#if defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_AFFINE)
+#if defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_SEMI)
+// the semi-global modes (nw_kscore_semi.hip: its own translation unit, default scheduler): single
+// pairs only, K = 2 and 4, int16 and int8 profiles
+namespace {
+
+constexpr int kRowMaxThreads = 1024;
+
+// Row R of a semi-global score launch (StripArgs::rowR) -> score and end column: H(R, j) = Hgo' - d +
+// (R + j) ge for j = 1 .. C together with the analytic H(R, 0) = go + (R - 1) ge, the smallest j that
+// attains the maximum.  One key per cell, value << 32 | ~j, compared as signed 64-bit.
+__global__ void __launch_bounds__(kRowMaxThreads) nw_semi_rowmax_kernel(const int* row, int R, int C, int dd, int go, int ge,
+                                                                        int* score, int* jend)
+{
+    __shared__ long long sk[kRowMaxThreads];
+    auto key = [](int v, int j) { return (long long)(((unsigned long long)(uint32_t)v << 32) | (uint32_t)~(uint32_t)j); };
+    long long best = key(go + (R - 1) * ge, 0);
+    for (int j = 1 + (int)threadIdx.x; j <= C; j += kRowMaxThreads)
+        best = max(best, key(row[kTapPad + j] - dd + (R + j) * ge, j));
+    sk[threadIdx.x] = best;
+    __syncthreads();
+    for (int n = kRowMaxThreads / 2; n > 0; n >>= 1)
+    {
+        if ((int)threadIdx.x < n) sk[threadIdx.x] = max(sk[threadIdx.x], sk[threadIdx.x + n]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+    {
+        score[0] = (int)(sk[0] >> 32);
+        jend[0] = (int)~(uint32_t)sk[0];
+    }
+}
+
+}  // namespace
+
+hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)
+{
+    if (a.nPairs != 1 || a.sched || a.bidiTop != 0 || a.tkFirst != 0 || a.tapRow != 0 || a.tapGran != 0 || !a.rowR || grid <= 0)
+        return hipErrorInvalidValue;
+    if (k == 2)
+    {
+        if (mode == kModeScoreSG) return launch_ksq<kModeScoreSG, 2, false>(a, grid, stream);
+        if (mode == kModeScoreSGL) return launch_ksq<kModeScoreSGL, 2, false>(a, grid, stream);
+        return hipErrorInvalidValue;
+    }
+    if (k != 4) return hipErrorInvalidValue;
+    if (mode == kModeScoreSG) return launch_ksq<kModeScoreSG, 4, false>(a, grid, stream);
+    if (mode == kModeScoreSGL) return launch_ksq<kModeScoreSGL, 4, false>(a, grid, stream);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream)
+{
+    hipLaunchKernelGGL(nw_semi_rowmax_kernel, dim3(1), dim3(kRowMaxThreads), 0, stream, rowR, R, C, go - ge, go, ge, score, jend);
+    return hipGetLastError();
+}
+#elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_AFFINE)
 // the affine modes (nw_kscore_ag.hip: its own translation unit, built with the iterative ILP
 // scheduler: 50k NW-AG 3.86 -> 3.73 ms, profiles/r04_score_k.txt)
 hipError_t launch_krow_score_affine(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)

@@ -21,9 +21,19 @@ constexpr int kModeScoreSW = 4;
 constexpr int kModeScoreSWL = 5;
 // NW (global) with a linear gap: the AG step without E' and F' (d = 0)
 constexpr int kModeScoreAGL = 6;
+// Score-only semi-global alignment (gsa_score_semi_dev: the whole query within the subject), affine
+// and linear: the global step under a free row 0 (H = 0 at every column, as the SW border), column 0
+// global; instead of the cell (R, C) the strip that holds row R stores that row's Hgo' over every
+// column (StripArgs::rowR), and a small kernel behind the fill takes its first maximum
+constexpr int kModeScoreSG = 7;
+constexpr int kModeScoreSGL = 8;
 __host__ __device__ constexpr bool is_sw_mode(int mode) { return mode == kModeScoreSW || mode == kModeScoreSWL; }
 __host__ __device__ constexpr bool is_ag_mode(int mode) { return mode == kModeScoreAG || mode == kModeScoreAGL; }
-__host__ __device__ constexpr bool is_lin_mode(int mode) { return mode == kModeScoreSWL || mode == kModeScoreAGL; }
+__host__ __device__ constexpr bool is_sg_mode(int mode) { return mode == kModeScoreSG || mode == kModeScoreSGL; }
+__host__ __device__ constexpr bool is_lin_mode(int mode)
+{
+    return mode == kModeScoreSWL || mode == kModeScoreAGL || mode == kModeScoreSGL;
+}
 __host__ __device__ constexpr bool is_score_mode(int mode) { return is_ag_mode(mode) || is_sw_mode(mode); }
 constexpr int kWaveRows = 256;                          // rows per strip (one wave, 4 rows per lane)
 constexpr int kSparseNS = 4;                            // strip waves per workgroup, sparse fills
@@ -150,6 +160,10 @@ struct StripArgs
     // pairs of the launch (include/gsa.h).  A table with a larger q sets error bit 2, as one outside
     // int16 does.
     int qcap;
+    // kModeScoreSG / SGL (nw_kscore_semi.hip): row R's Hgo' (H' when linear), shifted as the hand-off
+    // holds it, at rowR[kTapPad + column] for every column the lane that holds row R computes
+    // (columns -63 .. Cp + 79); launch_semi_rowmax unshifts it and takes the first maximum
+    int* rowR;
 };
 // Score batch (nw_krow.hip nw_kscore_kernel: sched set, or nPairs > 1 without bidiTop): swBest is
 // the base of two result words per pair, pair p's at swBest[2p] (NW: the result cell in the low

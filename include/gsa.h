@@ -773,6 +773,94 @@ int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int6
                                 int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
                                 char* cigar, int64_t cigar_cap, int64_t* cigar_need,
                                 gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
+/* Long pairs, semi-global mode: a whole query within one long subject.
+ * The alignment shape of "Database search, semi-global mode" above, word for word, for one pair of any
+ * length the K-rows score kernel takes (a read against a contig): seqY is the query (R letters, down
+ * the rows), seqX the subject (C letters, along the columns), gapo <= gape <= 0, and
+ *   row 0 is free:        H(0, j) = 0, E(0, j) = F(0, j) = minus infinity, j = 0 ... C;
+ *   column 0 is global:   H(i, 0) = F(i, 0) = gapo + (i - 1) gape, E(i, 0) = minus infinity, i >= 1;
+ *   inside, the Gotoh recurrences without the zero floor;
+ *   score = max over j = 0 ... C of H(R, j) -- column 0, the all-insert alignment, is a candidate;
+ *   end cell: i_end = R, j_end the SMALLEST j that attains the score.
+ * Scores may be negative.  C = 0: score gapo + (R - 1) gape, end cell (R, 0); R = 0: score 0, end cell
+ * (0, 0); both are answered on the host.  A caller who wants the subject global and the query's ends
+ * free swaps the two sequences and transposes the table.
+ *
+ * gsa_score_semi_dev takes gsa_score_dev's arguments without local and fills the same result struct.
+ * Synchronous.  The pair runs in one direction on the K-rows score kernel's semi-global instances
+ * (nw_kscore_semi.hip): the global step under a free row 0, with 4 rows per lane for linear gaps
+ * (gapo == gape) and 2 for affine ones, as gsa_score_dev picks them for a global pair; GSA_SCORE_K and
+ * GSA_KROW_Q8 are honoured as there and no other knob is read.  The strip that holds row R stores that
+ * row over every column into a row buffer of 4 (C + 208) bytes in the context's scratch (counted in
+ * gsa_mem_stats), a small kernel behind the fill takes its first maximum together with the analytic
+ * H(R, 0), and one copy brings score and end column back.
+ * This mode has no second path: the pair runs on that kernel or the call is refused.  With smax the
+ * largest |table value| (at least 1) and B = smax min(R, C) + |gapo| + (R + C) |gape| it is
+ * errorInvalidValue, before anything is enqueued, unless
+ *   B + |gapo| < 2^29                                  (gsa_score_dev's range of a global pair),
+ *   (R + C) |gape| + (gape - gapo) + smax < 2^28       (the shifted values' room in int32),
+ *   the score kernel's LDS (a profile of substsz rows) fits the device, and
+ *   every table value s has s - gapo - gape in (-32768, 32767]   (the kernel's int16 profile);
+ * the last is checked on the host from the table, which the call reads back in stream order anyway.
+ * Everything gsa_score_dev rejects is rejected here too.  The call adds no launch kind and no knob:
+ * the record of gsa_last_launch is left untouched, and the kernel reports errors in the score
+ * kernels' own control word, so the fills' sticky error word is left alone. */
+int gsa_score_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                       gsa_score_result* out, void* stream);
+
+typedef struct gsa_align_pair_semi_info {  /* what the call ran; optional out-parameter */
+    int32_t strip_rows;     /* TR: rows of a strip, the score kernel's ticket (512 or 1024) */
+    int32_t strips;         /* strips that hold the rows 1 ... R */
+    int32_t strips_filled;  /* strips filled with move codes, over all chunks */
+    int32_t chunks;         /* fill + walk launch pairs */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    int64_t j_window;       /* jW: codes are kept for the columns jW + 1 ... j_end only (0: from column 1) */
+    float score_ms, fill_ms, walk_ms; /* hipEvent time of the score launch, and of the fill and the walk launches
+                                         summed over the chunks */
+    int32_t pad0;
+} gsa_align_pair_semi_info;
+
+/* The semi-global alignment of one long pair, traced on the device: gsa_align_pair_dev's arguments
+ * without local, the same result struct and CIGAR buffer rules (one NUL-terminated string at cigar[0],
+ * status 2 when it does not fit cigar_cap with the cells still valid, *cigar_need the bytes it needs,
+ * 2 (R + C) + 1 always enough).  Synchronous.
+ * Semantics: score and end cell (R, j_end) are gsa_score_semi_dev's for the pair.  The walk goes
+ * backwards from (R, j_end) in state H under gsa_align_db_dev's rules -- diagonal before F before E at
+ * equal value, a gap extended only when that is strictly better than opening, column 0 F only -- and
+ * stops as soon as it is in row 0: i_start = 0, j_start the column it stopped in; no 'D' is emitted in
+ * row 0, so the subject's head and tail stay out of the CIGAR.  C = 0: score gapo + (R - 1) gape, cells
+ * (0, 0)-(R, 0), R x 'I'; R = 0: score 0, all cells (0, 0), an empty CIGAR; both on the host.
+ * How: gsa_score_semi_dev's launch leaves the bottom row of each of its tickets of TR rows (512, linear
+ * gaps 1024) in its hand-off rows.  Every strip of TR rows from row R's up to strip 0 -- the path
+ * always reaches row 0 -- is refilled with 4-bit move codes, one wave per strip, and one lane walks the
+ * codes (nw_pair_semi_trace.hip).  The codes are kept for a column window only.  With pmax = max(0,
+ * largest table value) and S the score, every alignment obeys S <= pmax R + d gape for its d letters
+ * of 'D', so for gape < 0 the path has at most dmax = floor((pmax R - S) / |gape|) of them and spans at
+ * most R + dmax columns: with
+ *   jW = max(0, j_end - R - dmax - 1)          (gape = 0: jW = 0)
+ * the fill treats column jW > 0 as minus infinity below row 0 (jW = 0: the true column 0) and computes
+ * the columns jW + 1 ... j_end; this is exact, ties included (nw_pair_semi_plan.h).  A strip's codes
+ * take (j_end - jW) TR / 2 bytes.  scratch_limit is the bytes of codes the call may hold at once; 0 is
+ * the default, 2 GiB.  When the strips do not all fit they are taken bottom-up in chunks of
+ * consecutive strips, a fill and a walk launch and one small copy back per chunk; a later chunk is
+ * filled only up to the column where the walk left the one below.  An end cell on column 0 (the
+ * all-insert alignment) needs no codes: chunks = 0.  The scratch is counted in the peaks of
+ * gsa_mem_stats.
+ * No result has status 1: the mode has no second path.  The call is errorInvalidValue, before anything
+ * is enqueued, for everything gsa_score_semi_dev refuses, for a pair whose value bound B reaches 2^26
+ * (the fill keeps 4 x value + source), for a negative scratch_limit or cigar_cap, a null out or a null
+ * cigar with cigar_cap > 0; and errorInvalidValue behind the score launch, which alone knows the
+ * window, for a scratch_limit below one strip's windowed codes.  A walk that reaches column jW > 0
+ * below row 0, which the bound excludes, is errorKernelFailure.  *info (may be null) says what the
+ * call ran.  The call adds no launch kind and no knob and leaves the record of gsa_last_launch and the
+ * fills' sticky error word alone.  *kernel_ms (may be null) gets the hipEvent time of all kernels of
+ * the call. */
+int gsa_align_pair_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                            int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                            int64_t* cigar_need, gsa_align_pair_semi_info* info, float* kernel_ms, void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
