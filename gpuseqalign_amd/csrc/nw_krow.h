@@ -68,5 +68,14 @@ hipError_t launch_krow_score_affine(const StripArgs& a, int mode, int k, int gri
 // go + (R - 1) ge) to *score and the smallest column that attains it to *jend.
 hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
 hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream);
+// Semi-global scores of a batch of independent pairs (nw_kscore_semi_batch.hip): launch_krow_score's
+// contract for a batch (ticketBase / nTickets / granOff, a.sched, a.swBest two zeroed words per pair,
+// grid <= 0: every resident slot) in the modes kModeScoreSG / SGL; pair p's row R goes to its own buffer
+// PairDesc::score of kTapPad + Cp + 80 ints, at a multiple of 16 ints.  launch_semi_rowmax_batch,
+// enqueued behind it, takes every pair's maximum as launch_semi_rowmax does, one workgroup per pair:
+// out[p] = {score, R, j_end, 0}, out[nPairs].score the error word *err (launch_score_finalize's layout).
+hipError_t launch_krow_score_semi_batch(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
+hipError_t launch_semi_rowmax_batch(const PairDesc* pairs, int nPairs, int go, int ge, const unsigned* err, ScoreOut* out,
+                                    hipStream_t stream);
 
 }  // namespace gsa

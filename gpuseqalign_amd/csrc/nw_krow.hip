@@ -2403,6 +2403,8 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
             pa.idxBits = sw_idx_bits(d.R, d.C);
             pa.tapRow = 0;
             pa.tapGran = 0;
+            // semi-global: the pair's own row buffer (score launches do not use PairDesc::score otherwise)
+            if constexpr (is_sg_mode(MODE)) pa.rowR = d.score;
         }
         else if (h == 1)
         {
@@ -2485,7 +2487,72 @@ hipError_t launch_ks(const StripArgs& a, int grid, hipStream_t stream)
 
 }  // namespace
 
-#if defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_SEMI)
+#if defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_SEMI_BATCH)
+// the semi-global modes over a batch of independent pairs (nw_kscore_semi_batch.hip: its own
+// translation unit, default scheduler): the BATCH instances, K = 2 and 4, int16 and int8 profiles
+namespace {
+
+constexpr int kRowMaxThreads = 1024;
+
+// nw_semi_rowmax_kernel (nw_kscore_semi.hip) per pair, one workgroup each: R, C and the row (PairDesc::
+// score) from the pair's descriptor, the same key (H << 32 | ~j, signed, the analytic H(R, 0) among the
+// candidates, the smallest j winning).  out[p] as launch_score_finalize lays it out, out[nPairs] the
+// launch's error word.
+__global__ void __launch_bounds__(kRowMaxThreads) nw_semi_rowmax_batch_kernel(const PairDesc* pairs, int nPairs, int dd, int go,
+                                                                              int ge, const unsigned* err, ScoreOut* out)
+{
+    __shared__ long long sk[kRowMaxThreads];
+    auto key = [](int v, int j) { return (long long)(((unsigned long long)(uint32_t)v << 32) | (uint32_t)~(uint32_t)j); };
+    const int p = blockIdx.x;
+    if (p >= nPairs) return;
+    const int R = pairs[p].R, C = pairs[p].C;
+    const int* const row = pairs[p].score;
+    long long best = key(go + (R - 1) * ge, 0);
+    for (int j = 1 + (int)threadIdx.x; j <= C; j += kRowMaxThreads)
+        best = max(best, key(row[kTapPad + j] - dd + (R + j) * ge, j));
+    sk[threadIdx.x] = best;
+    __syncthreads();
+    for (int n = kRowMaxThreads / 2; n > 0; n >>= 1)
+    {
+        if ((int)threadIdx.x < n) sk[threadIdx.x] = max(sk[threadIdx.x], sk[threadIdx.x + n]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+    {
+        out[p] = ScoreOut {(int)(sk[0] >> 32), R, (int)~(uint32_t)sk[0], 0};
+        if (p == 0) out[nPairs] = ScoreOut {(int)err[0], 0, 0, 0};
+    }
+}
+
+}  // namespace
+
+hipError_t launch_krow_score_semi_batch(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)
+{
+    // independent pairs, every pair's row buffer in its descriptor; grid <= 0: every resident slot
+    if (!a.pairs || a.nPairs < 1 || a.bidiTop != 0 || a.bidiMid != 0 || a.tkFirst != 0 || a.tapRow != 0 || a.tapGran != 0 ||
+        !a.swBest)
+        return hipErrorInvalidValue;
+    if (k == 2)
+    {
+        if (mode == kModeScoreSG) return launch_ksq<kModeScoreSG, 2, true>(a, grid, stream);
+        if (mode == kModeScoreSGL) return launch_ksq<kModeScoreSGL, 2, true>(a, grid, stream);
+        return hipErrorInvalidValue;
+    }
+    if (k != 4) return hipErrorInvalidValue;
+    if (mode == kModeScoreSG) return launch_ksq<kModeScoreSG, 4, true>(a, grid, stream);
+    if (mode == kModeScoreSGL) return launch_ksq<kModeScoreSGL, 4, true>(a, grid, stream);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_semi_rowmax_batch(const PairDesc* pairs, int nPairs, int go, int ge, const unsigned* err, ScoreOut* out,
+                                    hipStream_t stream)
+{
+    if (nPairs < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nw_semi_rowmax_batch_kernel, dim3((unsigned)nPairs), dim3(kRowMaxThreads), 0, stream, pairs, nPairs,
+                       go - ge, go, ge, err, out);
+    return hipGetLastError();
+}
+#elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_SEMI)
 // the semi-global modes (nw_kscore_semi.hip: its own translation unit, default scheduler): single
 // pairs only, K = 2 and 4, int16 and int8 profiles
 namespace {

@@ -1,0 +1,67 @@
+// nw_pair_semi_trace_batch.h -- the semi-global alignments of a batch of long pairs: the strips of many
+// pairs filled with 4-bit move codes over each pair's column window in one launch, seeded from the
+// batched score launch's checkpoint rows, and the pairs' walks side by side
+// (nw_pair_semi_trace_batch.hip); used by gsa_score.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nw_pair_semi_trace.h"
+#include "nw_pair_trace_batch.h"
+
+namespace gsa {
+
+// One pair of a round's fill: PairBatchDesc (iEnd = R; J the round's last column, stripBytes the codes
+// of one strip over the columns jW + 1 ... J) and the pair's window.
+struct SemiBatchDesc
+{
+    PairBatchDesc p;
+    int jW;  // column jW is the true column 0 (jW = 0) or minus infinity below row 0
+    int pad0;
+};
+
+// (a task is a PairBatchTask: pair, strip, code offset)
+struct SemiBatchFillArgs
+{
+    const SemiBatchDesc* pairs;
+    const PairBatchTask* tasks;  // by window width descending
+    int ntasks;
+    const int* subst;
+    int substsz;
+    int go, ge;
+    const unsigned long long* gran;   // the score launch's hand-off rows: Hgo', epoch << 32 | value
+    const unsigned long long* gran2;  // F' (affine gaps)
+    unsigned char* codes;
+    unsigned* counter;  // the task counter, zero before the launch
+};
+
+// One pair of a round's walk.
+struct SemiBatchWalk
+{
+    const int* seqY;
+    const int* seqX;
+    const unsigned char* codes;  // the pair's chunk: strip s at (s - tLo) stripBytes, column j at (j - jW - 1) TR / 2
+    long long stripBytes;
+    int tLo;    // the chunk's first strip
+    int iStop;  // stop on this row (> 0) at a column > 0: the chunk's upper boundary
+    int rec;    // index of the pair's record
+    int jW;
+    unsigned char* moves;  // one byte per move, last move first
+};
+
+struct SemiBatchWalkArgs
+{
+    const SemiBatchWalk* walks;
+    int nwalks;
+    int krShift;  // log2 KR: 3 or 4
+    SemiWalkRec* recs;
+};
+
+// a grid for ntasks fill tasks, at most maxWgs workgroups (0: all resident).  KR: 8 or 16
+hipError_t semi_batch_fill_grid(bool affine, int KR, int ntasks, int maxWgs, int* grid);
+// the fill of a round on `grid` workgroups, then the walks, one workgroup per pair up to walkGrid;
+// ev: three events recorded before the fill, between the two and after the walks
+hipError_t launch_semi_batch_trace(const SemiBatchFillArgs& f, const SemiBatchWalkArgs& w, int KR, int grid, int walkGrid,
+                                   hipEvent_t* ev, hipStream_t st);
+
+}  // namespace gsa
