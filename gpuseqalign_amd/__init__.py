@@ -148,6 +148,14 @@ class AlignPairSemiInfo(ctypes.Structure):
                 ("pad0", ctypes.c_int32)]
 
 
+class AlignPairOverlapInfo(ctypes.Structure):
+    """gsa_align_pair_overlap_info (include/gsa.h): what the last gsa_align_pair_overlap_dev call ran."""
+    _fields_ = [("strip_rows", ctypes.c_int32), ("strips", ctypes.c_int32), ("strips_filled", ctypes.c_int32),
+                ("chunks", ctypes.c_int32), ("code_bytes", ctypes.c_int64),
+                ("score_ms", ctypes.c_float), ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float),
+                ("pad0", ctypes.c_int32)]
+
+
 class AlignBatchInfo(ctypes.Structure):
     """gsa_align_batch_info (include/gsa.h): what the last gsa_align_batch_dev call ran."""
     _fields_ = [("batch_pairs", ctypes.c_int32), ("alone_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32),
@@ -258,6 +266,12 @@ SIGNATURES = {
     "gsa_align_pair_semi_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64,
                                                ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                                ctypes.POINTER(AlignPairSemiInfo), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_overlap_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32,
+                                             ctypes.POINTER(ScoreResult), _vp]),
+    "gsa_align_pair_overlap_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64,
+                                                  ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                                  ctypes.POINTER(_i64), ctypes.POINTER(AlignPairOverlapInfo),
+                                                  ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
@@ -685,6 +699,84 @@ class Engine:
         torch.cuda.synchronize(dev)
         return self.align_pair_semi_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
                                         gapo, gape, scratch_limit)
+
+    # -- long pairs, overlap (dovetail): a suffix of either sequence on a prefix of the other --
+    def score_overlap_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int, substsz: int,
+                          gapo: int, gape: Optional[int] = None, stream: Optional[int] = None) -> dict:
+        """Overlap (dovetail) score of one device-resident pair (gsa_score_overlap_dev; synchronous):
+        row 0 and column 0 are free, and the score is the largest value on the last row or the last
+        column -- a suffix of one sequence against a prefix of the other, or either within the other.
+        The arguments of score_semi_dev; gape defaults to gapo.  {"score", "i_end", "j_end",
+        "kernel_ms"}: the score is never negative; the end cell is the first cell of the last row that
+        attains it, or else the first such cell of the last column."""
+        r = ScoreResult()
+        st = lib().gsa_score_overlap_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                         gapo if gape is None else gape, ctypes.byref(r), stream)
+        self._check(st, "gsa_score_overlap_dev")
+        return {"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end),
+                "kernel_ms": float(r.calc_kernel_ms)}
+
+    def score_overlap(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None) -> dict:
+        """score_overlap_dev over host arrays: the sequences with the header element in front, as score()
+        takes them; sequences and table are uploaded through torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return self.score_overlap_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz, gapo,
+                                      gape)
+
+    def align_pair_overlap_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int,
+                               substsz: int, gapo: int, gape: Optional[int] = None, scratch_limit: int = 0,
+                               stream: Optional[int] = None) -> dict:
+        """The overlap alignment of one device-resident pair (gsa_align_pair_overlap_dev; synchronous):
+        the arguments of score_overlap_dev, and `scratch_limit`, the bytes of move codes held at once
+        (0: the default, 2 GiB).  {"score", "status", "i_start", "j_start", "i_end", "j_end", "cigar",
+        "kernel_ms"} as align_pair_semi_dev returns them; the start cell lies on row 0 or on column 0,
+        no overhang is in the CIGAR, status is 0 (never 1).  last_align_pair_overlap_info() says what ran."""
+        res = AlignDbResult()
+        info = AlignPairOverlapInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes always suffice
+        cap = 2 * (max(adjrows - 1, 0) + max(adjcols - 1, 0)) + 1
+        buf = ctypes.create_string_buffer(cap)
+        st = lib().gsa_align_pair_overlap_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                              gapo if gape is None else gape, int(scratch_limit), ctypes.byref(res),
+                                              buf, cap, ctypes.byref(need), ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_pair_overlap_dev")
+        self._align_pair_overlap_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                         for k, t in info._fields_ if k != "pad0"}
+        cig = buf.raw[res.cigar_off:res.cigar_off + res.cigar_len].decode() if res.status == 0 else ""
+        return {"score": int(res.score), "status": int(res.status), "i_start": int(res.i_start),
+                "j_start": int(res.j_start), "i_end": int(res.i_end), "j_end": int(res.j_end), "cigar": cig,
+                "kernel_ms": float(ms.value)}
+
+    def last_align_pair_overlap_info(self) -> dict:
+        """gsa_align_pair_overlap_info of the last align_pair_overlap_dev call on this engine:
+        "strip_rows", "strips" (those of the rows 1 ... i_end), "strips_filled", "chunks" (fill + walk
+        launch pairs), "code_bytes" (peak bytes of move codes held at once), "score_ms", "fill_ms" and
+        "walk_ms"."""
+        info = getattr(self, "_align_pair_overlap_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_pair_overlap_info: no align_pair_overlap_dev call yet")
+        return dict(info)
+
+    def align_pair_overlap(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None, scratch_limit: int = 0) -> dict:
+        """align_pair_overlap_dev over host arrays: the sequences with the header element in front, as
+        score() takes them; sequences and table are uploaded through torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return self.align_pair_overlap_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
+                                           gapo, gape, scratch_limit)
 
     def score_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
                         local: bool = False, stream: Optional[int] = None) -> list:

@@ -162,6 +162,8 @@ enum BufId
     // above): a round's task counter, task, pair and walk tables; the pairs' walk records
     kBufPairBatchTab,
     kBufPairBatchRec,
+    // overlap score of one long pair (gsa_score_overlap_dev): column C of every row of every ticket (ints)
+    kBufOvCol,
     // mlsppt: host-mapped per-tile-row words (epoch << 32 | column chunks in memory); a pinned host
     // buffer (>= kPtPin) the strided column chunks are packed into by copies on ptstream
     kBufPtFlags,  // mapped host memory

@@ -27,6 +27,8 @@
 #include "nw_pair_semi_trace.h"
 #include "nw_pair_semi_trace_batch.h"
 #include "nw_pair_semi_trace_batch_plan.h"
+#include "nw_pair_overlap_plan.h"
+#include "nw_pair_overlap_trace.h"
 #include "nw_pair_trace.h"
 #include "nw_pair_trace_batch.h"
 #include "nw_pair_trace_batch_plan.h"
@@ -2536,9 +2538,12 @@ struct SemiRoute
 // second path, then the K-rows score kernel's semi-global instance in one direction (row R into
 // kBufBidi) and the kernel that takes that row's first maximum; one copy brings score and end column
 // back.  gsa_last_launch's record and the fills' sticky error word are left alone.
+// overlap (gsa_score_overlap_dev): the same tests and geometry on the overlap instances, which store
+// column C of every row into kBufOvCol as well; the kernel behind them takes the maximum over row R and
+// column C and brings the end cell's row back too.
 int semi_pair_score(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t* seqX, int64_t C, const int32_t* subst,
                     int32_t substsz, int32_t gapo, int32_t gape, bool forAlign, gsa_score_result* out, hipStream_t st,
-                    SemiRoute* route)
+                    SemiRoute* route, bool overlap = false)
 {
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
@@ -2599,6 +2604,8 @@ int semi_pair_score(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t*
     if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
     // row R: columns -kTapPad .. C + 79, as the tap rows
     if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], (size_t)(gsa::kTapPad + C + 80) * sizeof(int))) != GSA_SUCCESS) return s;
+    // overlap: column C of the rows 0 ... tickets TR (every strip stores its rows, those past R too)
+    if (overlap && (s = reserve_hard(ctx, ctx->buf[kBufOvCol], (size_t)(tickets * TR + 1) * sizeof(int))) != GSA_SUCCESS) return s;
     unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
     unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
     a.pairs = ddesc;
@@ -2613,19 +2620,24 @@ int semi_pair_score(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t*
     a.swBest = sctl + 1;
     a.idxBits = sw_idx_bits(R, C);
     a.rowR = ctx->buf[kBufBidi].as<int>();
+    if (overlap) a.tapH = ctx->buf[kBufOvCol].as<int>();  // (no tap: tapRow stays 0)
     a.epoch = ++ctx->epoch;
     if (a.epoch == 0) a.epoch = ++ctx->epoch;
     if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
     (void)hipEventRecord(ctx->ev0, st);
     const int grid = std::max(1, std::min((int)tickets, ctx->cu_count));
-    const int mode = gapo == gape ? gsa::kModeScoreSGL : gsa::kModeScoreSG;
+    const int mode = overlap ? (gapo == gape ? gsa::kModeScoreOVL : gsa::kModeScoreOV)
+                             : (gapo == gape ? gsa::kModeScoreSGL : gsa::kModeScoreSG);
     // the int8 profile as score_ag_strip picks it (GSA_KROW_Q8)
     const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
     a.q8 = (q8env != 0 && (q8env == 2 || scoreK == 4) && gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
     a.q8flag = ctx->ctl + 2;
-    if ((e = gsa::launch_krow_score_semi(a, mode, scoreK, grid, st)) != hipSuccess ||
-        (e = gsa::launch_semi_rowmax(a.rowR, (int)R, (int)C, gapo, gape, (int*)sctl, (int*)(sctl + 1), st)) != hipSuccess)
+    // (overlap: score, i_end, j_end in the three ints at sctl; the error word at sctl + 3 stays clear of them)
+    if (overlap ? ((e = gsa::launch_krow_score_overlap(a, mode, scoreK, grid, st)) != hipSuccess ||
+                   (e = gsa::launch_overlap_max(a.rowR, a.tapH, (int)R, (int)C, gapo, gape, (int*)sctl, st)) != hipSuccess)
+                : ((e = gsa::launch_krow_score_semi(a, mode, scoreK, grid, st)) != hipSuccess ||
+                   (e = gsa::launch_semi_rowmax(a.rowR, (int)R, (int)C, gapo, gape, (int*)sctl, (int*)(sctl + 1), st)) != hipSuccess))
         return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
     (void)hipEventRecord(ctx->ev1, st);
@@ -2636,6 +2648,16 @@ int semi_pair_score(gsa_ctx* ctx, const int32_t* seqY, int64_t R, const int32_t*
     (void)hipEventElapsedTime(&out->calc_kernel_ms, ctx->ev0, ctx->ev1);
     if ((unsigned)res[3] != 0) return GSA_ERROR_KERNEL_FAILURE;
     out->score = (int32_t)(uint32_t)res[0];
+    if (overlap)
+    {
+        out->i_end = (int64_t)(int32_t)(uint32_t)(res[0] >> 32);
+        out->j_end = (int64_t)(int32_t)(uint32_t)res[1];
+        // a cell of row R or of column C, and never a negative score
+        if (out->score < 0 || out->i_end < 0 || out->i_end > R || out->j_end < 0 || out->j_end > C ||
+            (out->i_end != R && out->j_end != C))
+            return GSA_ERROR_KERNEL_FAILURE;
+        return GSA_SUCCESS;
+    }
     out->i_end = R;
     out->j_end = (int64_t)(int32_t)(uint32_t)res[1];
     if (out->j_end < 0 || out->j_end > C) return GSA_ERROR_KERNEL_FAILURE;
@@ -2809,6 +2831,179 @@ int align_pair_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, con
                 return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
             cig = fold_cigar(mv.data(), rec.n);
             r.i_start = 0;
+            r.j_start = rec.j;
+        }
+    }
+    const int64_t len = (int64_t)cig.size();
+    if (len + 1 <= cigar_cap)
+    {
+        std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
+        r.cigar_len = len;
+    }
+    else
+        r.status = 2;
+    if (cigar_need) *cigar_need = len + 1;
+    *out = r;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
+
+// gsa_score_overlap_dev: an empty side on the host (score 0 at (R, 0)), otherwise semi_pair_score on the
+// overlap instances.
+int score_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    const int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    out->calc_kernel_ms = 0.f;
+    if (R == 0 || C == 0)
+    {
+        // an empty side: every candidate is 0, and row R's first cell wins
+        out->score = 0;
+        out->i_end = R;
+        out->j_end = 0;
+        return GSA_SUCCESS;
+    }
+    return semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, false, out, st, nullptr, true);
+}
+
+// gsa_align_pair_overlap_dev: score and end cell from semi_pair_score's overlap launch, whose checkpoint
+// rows stay in kBufGran; then, bottom-up from i_end's strip, chunks of strips whose move codes over the
+// columns up to where the walk stands fit scratch_limit, a fill and a walk launch per chunk and one
+// small copy of the walk's record back (nw_pair_overlap_trace.hip), until the walk stands on row 0 or on
+// column 0; at the end the move bytes, folded into the CIGAR.  gsa_last_launch's record is left as it was.
+int align_pair_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
+                            gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                            gsa_align_pair_overlap_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_pair_overlap_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : (int64_t)gsa::kPairTraceScratch;
+    gsa_align_db_result r;
+    std::memset(&r, 0, sizeof(r));
+    // (an empty side, or score 0: the cells (R, 0)-(R, 0) and an empty CIGAR)
+    r.i_start = r.i_end = R;
+    std::string cig;
+    if (R > 0 && C > 0)
+    {
+        gsa_score_result sr {};
+        SemiRoute route;
+        if ((s = semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, true, &sr, st, &route, true)) != GSA_SUCCESS)
+            return s;
+        const KeepLaunchRecord keep(ctx);
+        hipError_t e = hipSuccess;
+        inf.score_ms = sr.calc_kernel_ms;
+        r.score = sr.score;
+        r.i_end = r.i_start = sr.i_end;
+        r.j_end = r.j_start = sr.j_end;
+        const int KR = route.K * gsa::kSparseNS;
+        const int64_t TR = 64 * (int64_t)KR;
+        const int64_t iEnd = sr.i_end, jEnd = sr.j_end;
+        inf.strip_rows = (int32_t)TR;
+        inf.strips = (int32_t)gsa::pair_strips(TR, iEnd);
+        // an end cell on a free border (score 0 at (R, 0), by the tie rule): no path, no codes
+        if (iEnd > 0 && jEnd > 0)
+        {
+            gsa::PairChunk ch;
+            // (a limit below one strip's codes: known only once j_end is)
+            if (!gsa::overlap_plan_chunk(TR, gsa::overlap_end_strip(TR, iEnd), jEnd, limit, &ch)) return GSA_ERROR_INVALID_VALUE;
+            if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
+                (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(iEnd + jEnd), 4096)) != GSA_SUCCESS)
+                return s;
+            for (hipEvent_t& ev : ctx->adbev)
+                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+            char* const meta = ctx->buf[kBufPairMeta].as<char>();
+            gsa::OverlapWalkRec* const drec = (gsa::OverlapWalkRec*)(meta + 64);
+            const size_t stride = (size_t)gsa::gran_stride((int)C);
+            gsa::OverlapWalkRec rec;
+            std::memset(&rec, 0, sizeof(rec));
+            rec.i = (int)iEnd;
+            rec.j = (int)jEnd;
+            rec.state = 4u;
+            if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            for (;;)
+            {
+                const int nstrips = (int)(ch.tHi - ch.tLo + 1);
+                if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
+                if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+                gsa::OverlapFillArgs f;
+                std::memset(&f, 0, sizeof(f));
+                f.seqY = seqY;
+                f.seqX = seqX;
+                f.subst = subst;
+                f.substsz = substsz;
+                f.go = gapo;
+                f.ge = gape;
+                f.iEnd = (int)iEnd;
+                f.J = (int)ch.J;
+                f.tLo = (int)ch.tLo;
+                f.nstrips = nstrips;
+                f.gran = ctx->buf[kBufGran].as<unsigned long long>();
+                f.gran2 = f.gran + (size_t)route.tickets * stride;
+                f.granStride = (long long)stride;
+                f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
+                f.stripBytes = ch.stripBytes;
+                f.counter = (unsigned*)meta;
+                gsa::OverlapWalkArgs w;
+                std::memset(&w, 0, sizeof(w));
+                w.seqY = seqY;
+                w.seqX = seqX;
+                w.codes = f.codes;
+                w.stripBytes = ch.stripBytes;
+                w.krShift = KR == 8 ? 3 : 4;
+                w.tLo = (int)ch.tLo;
+                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
+                w.rec = drec;
+                w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+                int grid = 1;
+                if ((e = gsa::overlap_fill_grid(gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
+                    (e = gsa::launch_overlap_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                note_launch(ctx);
+                if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                    (e = hipStreamSynchronize(st)) != hipSuccess)
+                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+                float m0 = 0.f, m1 = 0.f;
+                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+                inf.fill_ms += m0;
+                inf.walk_ms += m1;
+                inf.chunks += 1;
+                inf.strips_filled += nstrips;
+                inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
+                // a record out of range, or moves written past their buffer
+                if (rec.n < 0 || rec.n > iEnd + jEnd || rec.i < 0 || rec.i > iEnd || rec.j < 0 || rec.j > ch.J)
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                if (rec.done) break;
+                // on the chunk's upper boundary: the next chunk, for the columns up to here
+                if (!gsa::overlap_walk_goes_on(TR, ch, rec.i, rec.j) ||
+                    !gsa::overlap_plan_chunk(TR, ch.tLo - 1, rec.j, limit, &ch))
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            }
+            if (rec.i != 0 && rec.j != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            std::vector<unsigned char> mv((size_t)rec.n + 1);
+            if (rec.n > 0 &&
+                ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                 (e = hipStreamSynchronize(st)) != hipSuccess))
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            cig = fold_cigar(mv.data(), rec.n);
+            r.i_start = rec.i;
             r.j_start = rec.j;
         }
     }
@@ -3319,6 +3514,24 @@ int gsa_align_pair_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return align_pair_semi_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, scratch_limit, out, cigar,
                                 cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_pair_overlap_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
+                               gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                               gsa_align_pair_overlap_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_pair_overlap_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, scratch_limit, out, cigar,
+                                   cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_overlap_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                          const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out,
+                          void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_overlap_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, out, pick_stream(ctx, stream));
 }
 
 int gsa_score_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,

@@ -68,6 +68,15 @@ hipError_t launch_krow_score_affine(const StripArgs& a, int mode, int k, int gri
 // go + (R - 1) ge) to *score and the smallest column that attains it to *jend.
 hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
 hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream);
+// Overlap (dovetail) score of one pair (modes kModeScoreOV / OVL, nw_kscore_overlap.hip):
+// launch_krow_score_semi's contract with a free column 0 as well (H(i, 0) = 0), and besides row R at
+// a.rowR every strip of every ticket stores column C of its rows, shifted as row R is, at a.tapH[row]:
+// a buffer of 1 + nTickets x (256 k) ints (a.tapRow stays 0: no tap is taken).  launch_overlap_max,
+// enqueued behind it, unshifts both, adds H(R, 0) = H(0, C) = 0 and writes to res[0 .. 2] the largest
+// value and its cell (i_end, j_end): the smallest j of row R that attains it, or else the smallest i of
+// column C.
+hipError_t launch_krow_score_overlap(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
+hipError_t launch_overlap_max(const int* rowR, const int* colC, int R, int C, int go, int ge, int* res, hipStream_t stream);
 // Semi-global scores of a batch of independent pairs (nw_kscore_semi_batch.hip): launch_krow_score's
 // contract for a batch (ticketBase / nTickets / granOff, a.sched, a.swBest two zeroed words per pair,
 // grid <= 0: every resident slot) in the modes kModeScoreSG / SGL; pair p's row R goes to its own buffer

@@ -1593,6 +1593,48 @@ hipError_t launch_kr(const StripArgs& a, int grid, hipStream_t stream)
 // ====================================================================================
 constexpr int kNegS = -(1 << 29);  // "before the matrix": far from overflow, never the maximum
 typedef int int4u __attribute__((ext_vector_type(4), aligned(4)));  // 16 B at a 4-byte boundary (row R's stores)
+typedef int int2u __attribute__((ext_vector_type(2), aligned(4)));  // 8 B at a 4-byte boundary (column C's stores, K = 2)
+// m's bit of this lane ? b : a, the mask a scalar (the linear overlap instances' picks of column C: at a
+// given step one known lane stands on column C, so the mask needs no per-lane compare)
+__device__ __forceinline__ int ks_sel(int a, int b, uint64_t m)
+{
+    int r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
+    return r;
+}
+// x == 0 ? b[k] : a[k] for the K rows at once, one compare (the affine overlap instances' second body:
+// x counts this lane's steps down to the one that stands on column 0, or on column C)
+__device__ __forceinline__ void ks_sel0(int (&r)[2], const int (&a)[2], const int (&b)[2], int x)
+{
+    asm("v_cmp_eq_u32 vcc, 0, %6\n\tv_cndmask_b32 %0, %2, %4, vcc\n\tv_cndmask_b32 %1, %3, %5, vcc"
+        : "=&v"(r[0]), "=&v"(r[1])
+        : "v"(a[0]), "v"(a[1]), "v"(b[0]), "v"(b[1]), "v"(x)
+        : "vcc");
+}
+__device__ __forceinline__ void ks_sel0(int (&r)[4], const int (&a)[4], const int (&b)[4], int x)
+{
+    asm("v_cmp_eq_u32 vcc, 0, %12\n\tv_cndmask_b32 %0, %4, %8, vcc\n\tv_cndmask_b32 %1, %5, %9, vcc\n\t"
+        "v_cndmask_b32 %2, %6, %10, vcc\n\tv_cndmask_b32 %3, %7, %11, vcc"
+        : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(x)
+        : "vcc");
+}
+__device__ __forceinline__ void ks_sel0(int (&)[1], const int (&)[1], const int (&)[1], int) {}
+__device__ __forceinline__ uint64_t ks_lane_bit(int l) { return (unsigned)l < 64u ? 1ull << l : 0ull; }
+// a wave-uniform 64-bit value, in scalar registers whatever the compiler thought of it
+__device__ __forceinline__ uint64_t ks_uni64(uint64_t m)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+// which body of ks_strip's block: the plain one (0), or in the affine overlap mode the one with the floor
+// of column 0 and the picks of column C (1)
+template <int B>
+struct KsEdge
+{
+    static constexpr int value = B;
+};
 constexpr int kNegQ = -32768;      // profile value of the NEG column letter
 constexpr uint32_t kRing2Off = (uint32_t)(kKrowNSDefault + 1) * kRing * 4u;  // ring2 = ring + this
 
@@ -1623,7 +1665,9 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
     constexpr int NS = kKrowNSDefault, LW = 1024;
     constexpr bool AG = !is_lin_mode(MODE);  // E' and F' carried
     constexpr bool SW = is_sw_mode(MODE);
-    constexpr bool SG = is_sg_mode(MODE);  // semi-global: row R over every column instead of the cell (R, C)
+    // overlap: the semi-global instance with a free column 0 and column C of every row captured as well
+    constexpr bool OV = is_ov_mode(MODE);
+    constexpr bool SG = is_sg_mode(MODE) || OV;  // semi-global: row R over every column instead of the cell (R, C)
     const int Cp = a.Cp;
     const int ge = a.ge;
     const int dd = AG ? a.go - a.ge : 0;
@@ -1815,8 +1859,45 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
         rsel = (hasR && lane == laneR) ? kR : -1;
         rowB = (uint64_t)(uintptr_t)a.rowR + 4ull * (uint64_t)(kTapPad - lane);
     }
+    // overlap.  The free column 0: this lane stands on column 0 at step t = lane, in block lane >> 4 (the
+    // blocks 0 .. 3), and there its row k takes the floor H'(i, 0) = -i ge (H = 0), the SW modes' z at
+    // j = 0, folded into F' as they fold it.  F(i, 0) then is not minus infinity, but it feeds only F
+    // further down column 0, whose H takes the floor anyway: no H changes, and the hand-off carries the
+    // floored values on by itself.  A linear gap needs no select for it: H' of the left neighbour is E',
+    // so the rows start from H' = -i ge instead of minus infinity, and the columns < 1, whose NEG letter
+    // and lower rows above never exceed it, hand that value on to column 0 and from there, as E', to
+    // column 1 (H(i, 0) + ge: go = ge).  Column C: the lane reaches it at step C + lane (the blocks
+    // C >> 4 .. (C + 63) >> 4), keeps its K rows' Hgo' there and stores them once behind the block loop.
+    // Affine gaps: both selects live in a second instantiation of the block body, taken by the blocks
+    // 0 .. 3 and by column C's.  Linear gaps: one body, the picks of column C in a branch behind the steps
+    // that only its blocks take.  Every other block is the semi-global one.
+    int zc[OV ? K : 1], colv[OV ? K : 1];
+    if constexpr (OV)
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+        {
+            zc[k] = -(rl + k) * ge;
+            colv[k] = kNegS;
+            if constexpr (!AG) H[k] = zc[k];
+        }
+    }
 
-    auto block = [&](int b, int (&qc)[K][kQD], int (&qn)[K][kQD]) {
+    auto blockT = [&](int b, int (&qc)[K][kQD], int (&qn)[K][kQD], auto edge) {
+        // (affine gaps only: the second body does both, column 0's floor and the picks of column C)
+        constexpr bool FLOOR = OV && AG && decltype(edge)::value != 0;
+        // FLOOR: two per-lane counters and one compare on VCC per K selects (ks_sel0); scalar lane masks
+        // in their place kept enough SGPRs live across the block loop to spill more of them than the
+        // semi-global instance does (28-30 against 22 at K = 2, int16 profile)
+        [[maybe_unused]] int cz = 0, cc = 0;
+        [[maybe_unused]] int negk[OV ? K : 1], fl[OV ? K : 1];
+        if constexpr (FLOOR)
+        {
+            cz = lane - kBlk * b;         // steps until this lane stands on column 0 ...
+            cc = a.C + lane - kBlk * b;   // ... and on column C
+#pragma unroll
+            for (int k = 0; k < K; ++k) negk[OV ? k : 0] = kNegS;
+        }
         {
             const int pin = __builtin_amdgcn_readfirstlane(rpin), pco = __builtin_amdgcn_readfirstlane(rpco);
             const int pxo = (w == 0) ? __builtin_amdgcn_readfirstlane(rpxo) : 0;
@@ -1840,6 +1921,7 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
             const int upF = AG ? shr1z(FD) + hf[u >> 2][u & 3] : 0;
             int nh[K], ne[K], h[K];
             int f = 0;
+            if constexpr (FLOOR) ks_sel0(fl, negk, zc, cz - u);
 #pragma unroll
             for (int k = 0; k < K; ++k)
             {
@@ -1854,6 +1936,7 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
                 {
                     const int fprev = (k == 0) ? upF : f;
                     f = SW ? max3i(fprev, vup, zz[SW ? u + k : 0]) : max(fprev, vup);
+                    if constexpr (FLOOR) f = max(f, fl[OV ? k : 0]);
                     ne[k] = max(E[k], H[k]);
                     h[k] = max3i(dg, ne[k], f);
                     nh[k] = h[k] + dd;
@@ -1861,6 +1944,7 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
                 else
                 {
                     f = SW ? max(vup, zz[SW ? u + k : 0]) : vup;
+                    if constexpr (FLOOR) f = max(f, fl[OV ? k : 0]);
                     h[k] = max3i(dg, H[k], f);
                     nh[k] = h[k];
                 }
@@ -1887,7 +1971,19 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
                 if constexpr (AG) E[k] = ne[k];
                 if constexpr (!SW) va[k][u] = nh[k];
             }
+
             if constexpr (AG) FD = f;
+            if constexpr (FLOOR)
+            {
+                int nv[OV ? K : 1], pk[OV ? K : 1];
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+                {
+                    nv[OV ? k : 0] = nh[k];
+                    pk[OV ? k : 0] = colv[OV ? k : 0];
+                }
+                ks_sel0(colv, pk, nv, cc - u);
+            }
             if (u == kBlk - 2)
             {
                 asm volatile("" ::: "memory");
@@ -1947,6 +2043,24 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
         }
         else if constexpr (SG)
         {
+            if constexpr (OV && !AG)
+            {
+                // (uniform; linear gaps, which have no second body) a block with a lane on column C: at step
+                // u that is lane 16 b + u - C, which picks its K rows' values of that step out of the
+                // block's; under a scalar lane mask
+                const int bu = __builtin_amdgcn_readfirstlane(b), cu = __builtin_amdgcn_readfirstlane(a.C);
+                if (bu >= (cu >> 4) && bu <= ((cu + 63) >> 4))
+                {
+                    const int lc = kBlk * bu - cu;
+#pragma unroll
+                    for (int u = 0; u < kBlk; ++u)
+                    {
+                        const uint64_t mcu = ks_uni64(ks_lane_bit(lc + u));
+#pragma unroll
+                        for (int k = 0; k < K; ++k) colv[OV ? k : 0] = ks_sel(colv[OV ? k : 0], va[k][u], mcu);
+                    }
+                }
+            }
             // row R of this block: lane laneR's va[kR][u] is the Hgo' of column 16 b + u - laneR.  That
             // lane alone (the branch masks the others off: rsel < 0 in every other lane and in every
             // other strip) stores the 16 words, 64 B per block, at rowR[kTapPad + column]
@@ -1992,6 +2106,21 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
         }
         return true;
     };
+    auto block = [&](int b, int (&qc)[K][kQD], int (&qn)[K][kQD]) {
+        if constexpr (OV)
+        {
+            // (uniform) with an affine gap the blocks with a lane on column 0 or on column C take the second
+            // body.  (One body for both kinds: a third one, the floor alone, spilled VGPRs at K = 4 and
+            // measured 1.40-1.47 x the semi-global kernel at K = 2 against 1.14-1.25 x; and the picks in a
+            // branch behind the steps, as the linear instances have them, spilled VGPRs at K = 4 too.)
+            if constexpr (AG)
+            {
+                const int bu = __builtin_amdgcn_readfirstlane(b), cu = __builtin_amdgcn_readfirstlane(a.C);
+                if (bu < 4 || (bu >= (cu >> 4) && bu <= ((cu + 63) >> 4))) return blockT(b, qc, qn, KsEdge<1> {});
+            }
+        }
+        return blockT(b, qc, qn, KsEdge<0> {});
+    };
 
     if constexpr (SW) wv = 15u - 16u * (uint32_t)z0;
     for (int b = 0; b < NB; b += 2)
@@ -1999,6 +2128,16 @@ __device__ __forceinline__ void ks_strip(const StripArgs& a, const KsLds& L, int
         if (!block(b, qA, qB)) return;
         if (b + 1 >= NB) break;
         if (!block(b + 1, qB, qA)) return;
+    }
+    if constexpr (OV)
+    {
+        // column C of this lane's K rows, K consecutive words at tapH[rl] (rows past R too: the buffer
+        // holds every row of every ticket).  A global pointer, as row R's stores.
+        const uint64_t at = (uint64_t)(uintptr_t)a.tapH + 4ull * (uint64_t)rl;
+        if constexpr (K == 4)
+            *(gptr<int4u>)at = int4u {colv[0], colv[OV ? 1 : 0], colv[OV ? 2 : 0], colv[OV ? 3 : 0]};
+        else
+            *(gptr<int2u>)at = int2u {colv[0], colv[OV ? 1 : 0]};
     }
     if constexpr (SW)
     {
@@ -2063,8 +2202,9 @@ __device__ __forceinline__ void ks_feed(const StripArgs& a, const KsLds& L, int 
                 // row 0 shifted: global H'(0,c) = d for c >= 1 (0 at c = 0), local -c ge (H = 0);
                 // carried as Hgo' = H' + d; F' = -inf
                 // (semi-global: the local row, H = 0 at every column; column 0 then comes out global,
-                // the NEG letter at columns < 1 leaving only the F chain down from H(0, 0) = 0)
-                v = (is_sw_mode(MODE) || is_sg_mode(MODE)) ? dd - c * a.ge : (c == 0 ? dd : 2 * dd);
+                // the NEG letter at columns < 1 leaving only the F chain down from H(0, 0) = 0; overlap:
+                // the same row, column 0 floored in the strips)
+                v = (is_sw_mode(MODE) || is_sg_mode(MODE) || is_ov_mode(MODE)) ? dd - c * a.ge : (c == 0 ? dd : 2 * dd);
                 good = in;
             }
             else
@@ -2430,7 +2570,10 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
             const int r0 = tk * (64 * K * NS) + 64 * K * w + 1;
             const int rt = pa.tapRow - r0;
             __builtin_amdgcn_s_setprio(3);
-            if (pa.tapRow > 0 && rt >= 0 && rt < 64 * K && (rt + 1) % K == 0)
+            // (the overlap modes take no tap, and tapH is their column buffer: no TAP instance of theirs)
+            if constexpr (is_ov_mode(MODE))
+                ks_strip<MODE, Q8, K>(pa, L, tk, w, lane);
+            else if (pa.tapRow > 0 && rt >= 0 && rt < 64 * K && (rt + 1) % K == 0)
                 ks_strip<MODE, Q8, K, true>(pa, L, tk, w, lane, (rt + 1) / K - 1);
             else
                 ks_strip<MODE, Q8, K>(pa, L, tk, w, lane);
@@ -2605,6 +2748,72 @@ hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid,
 hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream)
 {
     hipLaunchKernelGGL(nw_semi_rowmax_kernel, dim3(1), dim3(kRowMaxThreads), 0, stream, rowR, R, C, go - ge, go, ge, score, jend);
+    return hipGetLastError();
+}
+#elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_OVERLAP)
+// the overlap modes (nw_kscore_overlap.hip: its own translation unit, default scheduler): single pairs
+// only, K = 2 and 4, int16 and int8 profiles
+namespace {
+
+constexpr int kOvMaxThreads = 1024;
+
+// Row R (StripArgs::rowR) and column C (StripArgs::tapH) of an overlap score launch -> score and end
+// cell.  H(R, j) = row[kTapPad + j] - d + (R + j) ge for j = 1 .. C, H(i, C) = col[i] - d + (i + C) ge
+// for i = 1 .. R, and the analytic H(R, 0) = H(0, C) = 0.  One signed 64-bit key per candidate: the
+// value << 32, then bit 31 set for a cell of row R, then the complement of j (row R) or of i (column
+// C) in the low 31 bits -- so the largest value wins, at equal value a cell of row R, there the
+// smallest j, otherwise the smallest i.  res[0] = score, res[1] = i_end, res[2] = j_end.
+__global__ void __launch_bounds__(kOvMaxThreads) nw_overlap_max_kernel(const int* row, const int* col, int R, int C, int dd, int ge,
+                                                                       int* res)
+{
+    __shared__ long long sk[kOvMaxThreads];
+    auto key = [](int v, bool onRow, int idx) {
+        return (long long)(((unsigned long long)(uint32_t)v << 32) | (onRow ? 0x80000000u : 0u) | (0x7fffffffu & ~(uint32_t)idx));
+    };
+    long long best = max(key(0, true, 0), key(0, false, 0));
+    for (int j = 1 + (int)threadIdx.x; j <= C; j += kOvMaxThreads)
+        best = max(best, key(row[kTapPad + j] - dd + (R + j) * ge, true, j));
+    for (int i = 1 + (int)threadIdx.x; i <= R; i += kOvMaxThreads) best = max(best, key(col[i] - dd + (i + C) * ge, false, i));
+    sk[threadIdx.x] = best;
+    __syncthreads();
+    for (int n = kOvMaxThreads / 2; n > 0; n >>= 1)
+    {
+        if ((int)threadIdx.x < n) sk[threadIdx.x] = max(sk[threadIdx.x], sk[threadIdx.x + n]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+    {
+        const uint32_t lo = (uint32_t)sk[0];
+        const bool onRow = (lo >> 31) != 0;
+        const int idx = (int)(0x7fffffffu & ~lo);
+        res[0] = (int)(sk[0] >> 32);
+        res[1] = onRow ? R : idx;
+        res[2] = onRow ? idx : C;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_krow_score_overlap(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)
+{
+    if (a.nPairs != 1 || a.sched || a.bidiTop != 0 || a.tkFirst != 0 || a.tapRow != 0 || a.tapGran != 0 || !a.rowR || !a.tapH ||
+        grid <= 0)
+        return hipErrorInvalidValue;
+    if (k == 2)
+    {
+        if (mode == kModeScoreOV) return launch_ksq<kModeScoreOV, 2, false>(a, grid, stream);
+        if (mode == kModeScoreOVL) return launch_ksq<kModeScoreOVL, 2, false>(a, grid, stream);
+        return hipErrorInvalidValue;
+    }
+    if (k != 4) return hipErrorInvalidValue;
+    if (mode == kModeScoreOV) return launch_ksq<kModeScoreOV, 4, false>(a, grid, stream);
+    if (mode == kModeScoreOVL) return launch_ksq<kModeScoreOVL, 4, false>(a, grid, stream);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_overlap_max(const int* rowR, const int* colC, int R, int C, int go, int ge, int* res, hipStream_t stream)
+{
+    hipLaunchKernelGGL(nw_overlap_max_kernel, dim3(1), dim3(kOvMaxThreads), 0, stream, rowR, colC, R, C, go - ge, ge, res);
     return hipGetLastError();
 }
 #elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_AFFINE)

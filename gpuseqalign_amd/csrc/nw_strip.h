@@ -27,12 +27,20 @@ constexpr int kModeScoreAGL = 6;
 // column (StripArgs::rowR), and a small kernel behind the fill takes its first maximum
 constexpr int kModeScoreSG = 7;
 constexpr int kModeScoreSGL = 8;
+// Score-only overlap (dovetail) alignment (gsa_score_overlap_dev: a suffix of either sequence against a
+// prefix of the other, or either within the other), affine and linear: the semi-global instance with a
+// free column 0 as well (the floor H'(i, 0) = -i ge at the one step a lane stands on column 0) and,
+// besides row R, column C of every row (StripArgs::tapH, K words per lane once per strip); a small
+// kernel behind the fill takes the first maximum over both (nw_kscore_overlap.hip)
+constexpr int kModeScoreOV = 9;
+constexpr int kModeScoreOVL = 10;
 __host__ __device__ constexpr bool is_sw_mode(int mode) { return mode == kModeScoreSW || mode == kModeScoreSWL; }
 __host__ __device__ constexpr bool is_ag_mode(int mode) { return mode == kModeScoreAG || mode == kModeScoreAGL; }
 __host__ __device__ constexpr bool is_sg_mode(int mode) { return mode == kModeScoreSG || mode == kModeScoreSGL; }
+__host__ __device__ constexpr bool is_ov_mode(int mode) { return mode == kModeScoreOV || mode == kModeScoreOVL; }
 __host__ __device__ constexpr bool is_lin_mode(int mode)
 {
-    return mode == kModeScoreSWL || mode == kModeScoreAGL || mode == kModeScoreSGL;
+    return mode == kModeScoreSWL || mode == kModeScoreAGL || mode == kModeScoreSGL || mode == kModeScoreOVL;
 }
 __host__ __device__ constexpr bool is_score_mode(int mode) { return is_ag_mode(mode) || is_sw_mode(mode); }
 constexpr int kWaveRows = 256;                          // rows per strip (one wave, 4 rows per lane)
@@ -136,6 +144,9 @@ struct StripArgs
     // bidiTop > 0: one launch runs both halves, pairs[0] (bidiTop tickets) and pairs[1] (the rest),
     // tickets alternating while both have some, then the longer half's; half 1 taps row tapRowB
     // into tapH / tapF + tapStride
+    // (kModeScoreOV / OVL, which take no tap: tapH is the column buffer -- row i's Hgo' (H' when linear)
+    // at column C, shifted as the hand-off holds it, at tapH[i] for every row of every strip, the rows
+    // past R included: 1 + nTickets x the ticket's rows ints; launch_overlap_max unshifts the rows 1 .. R)
     int* tapH;
     int* tapF;
     int tapRow;

@@ -946,6 +946,81 @@ int gsa_align_batch_semi_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
                              int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
                              int64_t* cigar_need, gsa_align_batch_semi_info* info, float* kernel_ms, void* stream);
 
+/* Long pairs, overlap (dovetail) mode: score and alignment of one pair.
+ * The suffix of one sequence against the prefix of the other (assembly, read merging, a read hanging
+ * over the end of a contig), or either sequence within the other.  seqY has R letters and runs down the
+ * rows, seqX has C letters and runs along the columns, both with the header element in front;
+ * gapo <= gape <= 0.
+ *   row 0 is free:     H(0, j) = 0, E = F = minus infinity, j = 0 ... C;
+ *   column 0 is free:  H(i, 0) = 0, E = F = minus infinity, i = 0 ... R;
+ *   inside, the Gotoh recurrences without the zero floor;
+ *   the candidates are the cells of row R (j = 0 ... C) and of column C (i = 0 ... R); score is the
+ *   largest H among them, so score >= 0 always;
+ *   end cell: if a cell of row R attains the score, (R, SMALLEST such j) -- gsa_score_semi_dev's rule on
+ *   that row --; otherwise (SMALLEST such i, C).  A score of 0 therefore always ends at (R, 0).
+ * The walk starts at the end cell in state H and follows gsa_align_db_dev's rules -- diagonal before F
+ * before E at equal value, a gap extended only when that is strictly better than opening -- and stops
+ * as soon as i = 0 or j = 0; (i_start, j_start) is the cell where it stopped.  No gap letters are
+ * emitted along either border, so all four overhangs stay out of the CIGAR; its letters are = X I D as
+ * elsewhere.  Score 0: cells (R, 0)-(R, 0), an empty CIGAR, status 0, no fill launched (chunks = 0).
+ * R = 0 or C = 0: score 0 with the cells that rule gives, (R, 0)-(R, 0), answered on the host.
+ * The one call covers all four arrangements: X's suffix on Y's prefix, Y's suffix on X's prefix, Y
+ * inside X, X inside Y.
+ *
+ * gsa_score_overlap_dev takes gsa_score_semi_dev's arguments and fills the same result struct.
+ * Synchronous.  The pair runs in one direction on the K-rows score kernel's overlap instances
+ * (nw_kscore_overlap.hip), the semi-global instances with two additions that live in a few blocks of a
+ * strip: the floor H = 0 at the one step a lane stands on column 0, and column C of every row, which
+ * every strip of every ticket stores once into a column buffer of 4 (1 + TR ceil(R / TR)) bytes in
+ * the context's scratch (counted in gsa_mem_stats) next to the semi-global row buffer.  A small kernel
+ * behind the fill takes the maximum over row R, column C and the analytic H(R, 0) = H(0, C) = 0 under
+ * the tie rule above, and one copy brings score and end cell back.  GSA_SCORE_K and GSA_KROW_Q8 are
+ * honoured as in gsa_score_semi_dev and no other knob is read.
+ * The mode has no second path.  It is errorInvalidValue, before anything is enqueued, for everything
+ * gsa_score_semi_dev refuses, under the same four conditions on B, the span, the LDS and the int16
+ * table window.  The call adds no launch kind and no knob: the record of gsa_last_launch is left
+ * untouched, and the kernel reports errors in the score kernels' own control word. */
+int gsa_score_overlap_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                          const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                          gsa_score_result* out, void* stream);
+
+typedef struct gsa_align_pair_overlap_info {  /* what the call ran; optional out-parameter */
+    int32_t strip_rows;     /* TR: rows of a strip, the score kernel's ticket (512 or 1024) */
+    int32_t strips;         /* strips that hold the rows 1 ... i_end */
+    int32_t strips_filled;  /* strips filled with move codes, over all chunks */
+    int32_t chunks;         /* fill + walk launch pairs */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    float score_ms, fill_ms, walk_ms; /* hipEvent time of the score launch, and of the fill and the walk launches
+                                         summed over the chunks */
+    int32_t pad0;
+} gsa_align_pair_overlap_info;
+
+/* The overlap alignment of one long pair, traced on the device: gsa_align_pair_semi_dev's arguments,
+ * result struct and CIGAR buffer rules (one NUL-terminated string at cigar[0], status 2 when it does
+ * not fit cigar_cap with the cells still valid, *cigar_need the bytes it needs, 2 (R + C) + 1 always
+ * enough).  Synchronous.  Score, end cell, walk and start cell are as stated above.
+ * How: gsa_score_overlap_dev's launch leaves the bottom row of each of its tickets of TR rows (512,
+ * linear gaps 1024) in its hand-off rows.  The strips from the one that holds i_end upwards are
+ * refilled with 4-bit move codes over the columns 1 ... j_end, one wave per strip, under the borders
+ * above (nw_pair_overlap_trace.hip), and one lane walks the codes; an end cell on column C above row R
+ * leaves the strips below it alone.  A strip's codes take j_end TR / 2 bytes: codes run from column 1,
+ * there is no column window.  scratch_limit is the bytes of codes the call may hold at once; 0 is the
+ * default, 2 GiB.  The strips are taken bottom-up in chunks of consecutive strips that fit, a fill and
+ * a walk launch and one small copy back per chunk; a later chunk is filled only up to the column where
+ * the walk left the one below, and the strips above the chunk in which the walk reached column 0 are
+ * not filled at all.  The scratch is counted in the peaks of gsa_mem_stats.
+ * No result has status 1.  The call is errorInvalidValue, before anything is enqueued, for everything
+ * gsa_score_overlap_dev refuses, for a pair whose value bound B reaches 2^26 (the fill keeps 4 x value
+ * + source), for a negative scratch_limit or cigar_cap, a null out or a null cigar with cigar_cap > 0;
+ * and errorInvalidValue behind the score launch, which alone knows j_end, for a scratch_limit below one
+ * strip's codes.  *info (may be null) says what the call ran.  The call adds no launch kind and no knob
+ * and leaves the record of gsa_last_launch and the fills' sticky error word alone.  *kernel_ms (may be
+ * null) gets the hipEvent time of all kernels of the call. */
+int gsa_align_pair_overlap_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                               int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                               int64_t* cigar_need, gsa_align_pair_overlap_info* info, float* kernel_ms, void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
