@@ -174,6 +174,15 @@ class AlignBatchSemiInfo(ctypes.Structure):
                 ("pad0", ctypes.c_int32)]
 
 
+class AlignBatchOverlapInfo(ctypes.Structure):
+    """gsa_align_batch_overlap_info (include/gsa.h): what the last gsa_align_batch_overlap_dev call ran."""
+    _fields_ = [("batch_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32), ("strip_rows", ctypes.c_int32),
+                ("strips", ctypes.c_int32), ("strips_filled", ctypes.c_int32), ("rounds", ctypes.c_int32),
+                ("code_bytes", ctypes.c_int64), ("gran_bytes", ctypes.c_int64),
+                ("score_ms", ctypes.c_float), ("fill_ms", ctypes.c_float), ("walk_ms", ctypes.c_float),
+                ("pad0", ctypes.c_int32)]
+
+
 class DbHit(ctypes.Structure):
     """gsa_db_hit (include/gsa.h): one ranked subject of a query of gsa_score_db_multi_dev."""
     _fields_ = [("subject", ctypes.c_int32), ("score", ctypes.c_int32), ("i_end", ctypes.c_int32),
@@ -291,6 +300,12 @@ SIGNATURES = {
     "gsa_align_batch_semi_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32, _i64,
                                                 ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                                 ctypes.POINTER(AlignBatchSemiInfo), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_overlap_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32,
+                                                   ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_batch_overlap_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32, _i64,
+                                                   ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                                   ctypes.POINTER(AlignBatchOverlapInfo), ctypes.POINTER(ctypes.c_float),
+                                                   _vp]),
     "gsa_score_db_multi_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64), _i32, _vp,
                                               _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
                                               ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
@@ -1138,6 +1153,82 @@ class Engine:
         element in front, as score_batch() takes them; sequences and table are uploaded through torch."""
         ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
         return self.align_batch_semi_dev(ptrs, dS, substsz, gapo, gape, 0, scratch_limit)
+
+    # -- long pairs, overlap (dovetail): scores and alignments of a batch in one call (DESIGN.md 2.2n) --
+
+    def score_overlap_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                                stream: Optional[int] = None) -> list:
+        """Overlap scores of many device-resident pairs in one launch (gsa_score_overlap_batch_dev;
+        synchronous).  `pairs`: sequence of (seqY_ptr, adjrows, seqX_ptr, adjcols), as
+        score_semi_batch_dev takes it.  One dict per pair, in order, equal to score_overlap_dev's for
+        that pair alone except "kernel_ms", which is the hipEvent time of the whole call's kernels in
+        every dict."""
+        n = len(pairs)
+        arr = (PairDev * max(n, 1))()
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+        res = (ScoreResult * max(n, 1))()
+        ms = ctypes.c_float(0.0)
+        st = lib().gsa_score_overlap_batch_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                               res, ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_overlap_batch_dev")
+        return [{"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end), "kernel_ms": float(ms.value)}
+                for r in res[:n]]
+
+    def score_overlap_batch(self, pairs, subst, gapo: int, gape: Optional[int] = None) -> list:
+        """score_overlap_batch_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the header
+        element in front, as score_batch() takes them; sequences and table are uploaded through torch."""
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.score_overlap_batch_dev(ptrs, dS, substsz, gapo, gape)
+
+    def align_batch_overlap_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                                max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None) -> list:
+        """The overlap alignments of many device-resident long pairs, traced on the device together
+        (gsa_align_batch_overlap_dev; synchronous).  `pairs` as score_overlap_batch_dev takes it.  One
+        dict per pair, in order, with align_pair_overlap_dev's keys and, "kernel_ms" apart (the hipEvent
+        time of the whole call's kernels in every dict), its values for that pair alone; "status" 1: one
+        strip of the pair's codes exceeds `scratch_limit` (score and end cell only).  `max_workgroups`
+        caps the grids of the fill and of the walk (0: all resident), `scratch_limit` the bytes of move
+        codes held at once (0: the default, 8 GiB).  last_align_batch_overlap_info() says what ran."""
+        n = len(pairs)
+        arr = (PairDev * max(n, 1))()
+        cap = 0
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+            cap += 2 * (max(ar - 1, 0) + max(ac - 1, 0)) + 1  # 2 (R + C) + 1 bytes always suffice
+        res = (AlignDbResult * max(n, 1))()
+        info = AlignBatchOverlapInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        st = lib().gsa_align_batch_overlap_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                               int(max_workgroups), int(scratch_limit), res, buf, cap, ctypes.byref(need),
+                                               ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_batch_overlap_dev")
+        self._align_batch_overlap_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                          for k, t in info._fields_ if not k.startswith("pad")}
+        raw = buf.raw
+        return [{"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start), "j_start": int(r.j_start),
+                 "i_end": int(r.i_end), "j_end": int(r.j_end),
+                 "cigar": raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else "",
+                 "kernel_ms": float(ms.value)} for r in res[:n]]
+
+    def last_align_batch_overlap_info(self) -> dict:
+        """gsa_align_batch_overlap_info of the last align_batch_overlap_dev call on this engine:
+        "batch_pairs" (traced on the device), "host_pairs", "strip_rows", "strips" (those of the rows
+        1 ... i_end, over the traced pairs), "strips_filled", "rounds" (fill + walk launch pairs),
+        "code_bytes" (peak bytes of move codes held at once), "gran_bytes" (checkpoint rows the score
+        launch kept), "score_ms", "fill_ms" and "walk_ms"."""
+        info = getattr(self, "_align_batch_overlap_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_batch_overlap_info: no align_batch_overlap_dev call yet")
+        return dict(info)
+
+    def align_batch_overlap(self, pairs, subst, gapo: int, gape: Optional[int] = None, scratch_limit: int = 0) -> list:
+        """align_batch_overlap_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the header
+        element in front, as score_batch() takes them; sequences and table are uploaded through torch."""
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.align_batch_overlap_dev(ptrs, dS, substsz, gapo, gape, 0, scratch_limit)
 
     # -- many queries against one database in one call (DESIGN.md 2.2f) ----------------------
 

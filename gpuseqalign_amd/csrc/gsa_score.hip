@@ -29,6 +29,8 @@
 #include "nw_pair_semi_trace_batch_plan.h"
 #include "nw_pair_overlap_plan.h"
 #include "nw_pair_overlap_trace.h"
+#include "nw_pair_overlap_trace_batch.h"
+#include "nw_pair_overlap_trace_batch_plan.h"
 #include "nw_pair_trace.h"
 #include "nw_pair_trace_batch.h"
 #include "nw_pair_trace_batch_plan.h"
@@ -3484,9 +3486,501 @@ int align_batch_semi_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
     return GSA_SUCCESS;
 }
 
+
+// What score_overlap_batch_impl's launch ran (gsa_align_batch_overlap_dev reads the checkpoint rows it
+// left in kBufGran: pair p's row t at granOff[p] + t gran_stride(C), the affine second array granTotal
+// words behind).
+struct OverlapBatchRoute
+{
+    int K = 0;                       // rows per lane of the K-rows launch; 0: nothing was launched
+    long long granTotal = 0;         // words of the first array, over all pairs
+    std::vector<int> tickets;        // per pair of the call: its tickets (0: an empty side)
+    std::vector<long long> granOff;  // its first row, in words
+};
+
+// gsa_score_overlap_batch_dev: score_semi_batch_impl next to score_overlap_impl.  Pairs with an empty
+// side on the host (score 0 at (R, 0)); for the others semi_pair_score's range tests for the overlap
+// instances, per pair, then the batched overlap instances of the K-rows score kernel in one launch --
+// every pair's row R into its own part of kBufBidi (PairDesc::score), column C of every row of every one
+// of its tickets into its own part of kBufOvCol (PairDesc::hcol) -- and one workgroup per pair that takes
+// the first maximum over both; one copy brings every score and end cell back.  gsa_last_launch's record
+// and the fills' sticky error word are left alone.
+int score_overlap_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                             int32_t gapo, int32_t gape, bool forAlign, gsa_score_result* out, float* batch_ms, hipStream_t st,
+                             OverlapBatchRoute* route = nullptr)
+{
+    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+    if (batch_ms) *batch_ms = 0.f;
+    if (route)
+    {
+        *route = OverlapBatchRoute {};
+        route->tickets.assign((size_t)npairs, 0);
+        route->granOff.assign((size_t)npairs, 0);
+    }
+    std::vector<int> bp;
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows > 1 && pairs[p].adjcols > 1) bp.push_back(p);
+    // the answers are written once nothing can refuse the call any more: a refusal leaves out as it was
+    auto host_pairs = [&]() {
+        for (int p = 0; p < npairs; ++p)
+        {
+            const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+            out[p].calc_kernel_ms = 0.f;
+            if (R == 0 || C == 0)
+            {
+                // an empty side: every candidate is 0, and row R's first cell wins (score_overlap_impl)
+                out[p].score = 0;
+                out[p].i_end = R;
+                out[p].j_end = 0;
+            }
+        }
+    };
+    if (bp.empty())
+    {
+        host_pairs();
+        return GSA_SUCCESS;
+    }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+    if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    const long long smax = subst_absmax(sub.data(), substsz);
+    if (gsa::krow_score_lds_bytes(substsz) > (size_t)ctx->lds_max) return GSA_ERROR_INVALID_VALUE;
+    // the kernel's own test of the shifted table (nw_kscore_kernel: error bit 2)
+    for (const int32_t v0 : sub)
+    {
+        const long long v = (long long)v0 - gapo - gape;
+        if (v <= -32768 || v > 32767) return GSA_ERROR_INVALID_VALUE;
+    }
+    // rows per lane as score_semi_batch_impl picks them: 4 in both gap models
+    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
+    const int scoreK = kenv == 2 ? 2 : 4;
+    const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
+    const int nb = (int)bp.size();
+    std::vector<gsa::PairDesc> hd;
+    std::vector<long long> rowOff, colOff;  // ints: the pair's row within kBufBidi, its column within kBufOvCol
+    long long tickets = 0, gran = 0, rowInts = 0, colInts = 0;
+    for (int p : bp)
+    {
+        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+        // semi_pair_score's tests, per pair
+        bool stripOk = false;
+        const int s = score_ranges(R, C, smax, gapo, gape, 0, &stripOk);
+        if (s != GSA_SUCCESS) return s;
+        if (!stripOk) return GSA_ERROR_INVALID_VALUE;  // span < 2^28: the shifted values' room in int32
+        // the fill keeps 4 x value + source (align_pair_impl's bound)
+        if (forAlign && smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= gsa::kDbTraceMaxValue)
+            return GSA_ERROR_INVALID_VALUE;
+        gsa::PairDesc d;
+        std::memset(&d, 0, sizeof(d));
+        d.seqY = pairs[p].seqY;
+        d.seqX = pairs[p].seqX;
+        d.R = (int)R;
+        d.C = (int)C;
+        d.Cp = (int)C;
+        d.nTickets = (int)((R + TR - 1) / TR);
+        d.ticketBase = (int)tickets;
+        d.granOff = gran;
+        tickets += d.nTickets;
+        gran += (long long)d.nTickets * gsa::gran_stride(d.Cp);
+        if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
+        // row R: columns -kTapPad .. C + 79, as the tap rows
+        rowOff.push_back(rowInts);
+        rowInts += ((long long)gsa::kTapPad + C + 80 + 15) & ~15ll;
+        // column C: the rows 0 ... nTickets TR -- every strip of every ticket stores its K words per lane,
+        // rows past R included, so the pair's last ticket counts whole; a column starts at a multiple of
+        // 16 ints, which keeps every store the alignment it has in the single call
+        colOff.push_back(colInts);
+        colInts += (1 + (long long)d.nTickets * TR + 15) & ~15ll;
+        hd.push_back(d);
+    }
+    // every buffer before anything is launched
+    int s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], (size_t)rowInts * sizeof(int))) != GSA_SUCCESS) return s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufOvCol], (size_t)colInts * sizeof(int))) != GSA_SUCCESS) return s;
+    int* const rows = ctx->buf[kBufBidi].as<int>();
+    int* const cols = ctx->buf[kBufOvCol].as<int>();
+    for (int i = 0; i < nb; ++i)
+    {
+        hd[(size_t)i].score = rows + rowOff[(size_t)i];
+        hd[(size_t)i].hcol = cols + colOff[(size_t)i];
+    }
+    if ((s = ensure_gran(ctx, 2 * (size_t)gran, st)) != GSA_SUCCESS) return s;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
+    // two result words per pair (unused by these modes), then the answers and the error word's
+    const size_t resBytes = (size_t)nb * 2 * sizeof(unsigned long long);
+    const size_t outBytes = ((size_t)nb + 1) * sizeof(gsa::ScoreOut);
+    if ((s = reserve_hard(ctx, ctx->buf[kBufSbatch], resBytes + outBytes, 4096)) != GSA_SUCCESS) return s;
+    const std::vector<int> sched = batch_schedule(ctx, hd, tickets);
+    if ((s = stage_descs(ctx, hd, sched, st)) != GSA_SUCCESS) return s;
+    if (route)
+    {
+        route->K = scoreK;
+        route->granTotal = gran;
+        for (int i = 0; i < nb; ++i)
+        {
+            route->tickets[(size_t)bp[(size_t)i]] = hd[(size_t)i].nTickets;
+            route->granOff[(size_t)bp[(size_t)i]] = hd[(size_t)i].granOff;
+        }
+    }
+    const KeepLaunchRecord keep(ctx);
+    gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
+    unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
+    unsigned long long* const res = ctx->buf[kBufSbatch].as<unsigned long long>();
+    gsa::ScoreOut* const dout = (gsa::ScoreOut*)(ctx->buf[kBufSbatch].as<char>() + resBytes);
+    gsa::StripArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.subst = subst;
+    a.substsz = substsz;
+    a.g = gapo;
+    a.go = gapo;
+    a.ge = gape;
+    a.ns = gsa::kSparseNS;
+    a.pairs = ddesc;
+    a.nPairs = nb;
+    a.nTicketsTotal = (int)tickets;
+    a.sched = sched.empty() ? nullptr : (const int*)(ddesc + nb);
+    a.gran = dgran;
+    a.gran2 = dgran + gran;
+    a.ticket = ctx->ctl;
+    a.err = (unsigned*)(sctl + 3);  // the score kernels' own error word (score_ag_strip)
+    a.spin = ctx->spin_ticks;
+    a.swBest = res;
+    a.rowR = rows;  // (every pair's own row and column come from its descriptor)
+    a.tapH = cols;  // (no tap: tapRow stays 0)
+    a.epoch = ++ctx->epoch;
+    if (a.epoch == 0) a.epoch = ++ctx->epoch;
+    if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess ||
+        (e = hipMemsetAsync(res, 0, resBytes, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    (void)hipEventRecord(ctx->ev0, st);
+    const int mode = gapo == gape ? gsa::kModeScoreOVL : gsa::kModeScoreOV;
+    // the int8 profile for linear gaps only, as score_semi_batch_impl picks it.  GSA_KROW_Q8=0 / 2: int16 / int8 always
+    const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
+    a.q8 = (q8env != 0 && (q8env == 2 || mode == gsa::kModeScoreOVL) &&
+            gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+    a.q8flag = ctx->ctl + 2;
+    // one pair: one workgroup per CU (its tickets are a chain); a batch: all resident slots
+    const int grid = nb == 1 ? std::max(1, std::min((int)tickets, ctx->cu_count)) : 0;
+    if ((e = gsa::launch_krow_score_overlap_batch(a, mode, scoreK, grid, st)) != hipSuccess ||
+        (e = gsa::launch_overlap_max_batch(ddesc, nb, gapo, gape, a.err, dout, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    note_launch(ctx);
+    (void)hipEventRecord(ctx->ev1, st);
+    std::vector<gsa::ScoreOut> ho((size_t)nb + 1);
+    if ((e = hipMemcpyAsync(ho.data(), dout, outBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    if (batch_ms) *batch_ms = ms;
+    if ((unsigned)ho[(size_t)nb].score != 0) return GSA_ERROR_KERNEL_FAILURE;
+    // a cell of row R or of column C, and never a negative score
+    for (int i = 0; i < nb; ++i)
+    {
+        const gsa::ScoreOut& o = ho[(size_t)i];
+        const int R = hd[(size_t)i].R, C = hd[(size_t)i].C;
+        if (o.score < 0 || o.i_end < 0 || o.i_end > R || o.j_end < 0 || o.j_end > C || (o.i_end != R && o.j_end != C))
+            return GSA_ERROR_KERNEL_FAILURE;
+    }
+    host_pairs();
+    for (int i = 0; i < nb; ++i)
+    {
+        const gsa::ScoreOut& o = ho[(size_t)i];
+        gsa_score_result& r = out[bp[(size_t)i]];
+        r.score = o.score;
+        r.i_end = o.i_end;
+        r.j_end = o.j_end;
+    }
+    return GSA_SUCCESS;
+}
+
+// gsa_align_batch_overlap_dev: every pair's score and end cell from score_overlap_batch_impl, whose
+// checkpoint rows stay in kBufGran, every pair in its own granules; then rounds that fit scratch_limit
+// (nw_pair_overlap_trace_batch_plan.h), bottom-up from each pair's end row's strip: one fill launch over
+// the strips of many pairs, one walk launch with a wave per pair and one small copy back per round
+// (nw_pair_overlap_trace_batch.hip), until every walk stands on row 0 or on column 0; at the end the
+// move bytes of all pairs in one copy, folded into the CIGARs.  gsa_last_launch's record is left as it was.
+int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                             int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
+                             gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                             gsa_align_batch_overlap_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+    if (scratch_limit < 0 || cigar_cap < 0 || max_workgroups < 0 || (cigar_cap > 0 && !cigar)) return GSA_ERROR_INVALID_VALUE;
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_batch_overlap_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    if (info) *info = inf;
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : (int64_t)gsa::kPairBatchScratch;
+    std::vector<gsa_align_db_result> res((size_t)npairs);
+    std::memset(res.data(), 0, res.size() * sizeof(gsa_align_db_result));
+    std::vector<std::string> cig((size_t)npairs);
+    const KeepLaunchRecord keep(ctx);
+    OverlapBatchRoute route;
+    std::vector<gsa_score_result> sres((size_t)npairs);
+    {
+        const int s = score_overlap_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, true, sres.data(), &inf.score_ms,
+                                               st, &route);
+        if (s != GSA_SUCCESS) return s;
+    }
+    const int K = route.K;
+    const int KR = K * gsa::kSparseNS;
+    const int64_t TR = 64 * (int64_t)KR;
+    inf.strip_rows = (int32_t)TR;                    // (0: every pair has an empty side)
+    inf.gran_bytes = 16 * (int64_t)route.granTotal;  // both arrays, 8-byte words
+    // the traced pairs: an end cell off both free borders, one strip within the limit
+    struct Bp
+    {
+        int p;  // index into pairs
+        int64_t iEnd, jEnd, movOff;
+    };
+    std::vector<Bp> bp;
+    int64_t movTotal = 0;
+    for (int p = 0; p < npairs; ++p)
+    {
+        gsa_align_db_result& r = res[(size_t)p];
+        r.score = sres[(size_t)p].score;
+        r.i_end = r.i_start = sres[(size_t)p].i_end;
+        r.j_end = r.j_start = sres[(size_t)p].j_end;
+        if (r.i_end == 0 || r.j_end == 0)
+        {
+            // an empty side, or score 0 at (R, 0) by the tie rule: no path, no codes
+            inf.host_pairs += 1;
+            continue;
+        }
+        if (!(K == 2 || K == 4)) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+        if (gsa::pair_strip_bytes(TR, r.j_end) > limit)
+        {
+            r.status = 1;  // one strip's codes exceed the limit: score and end cell only
+            r.i_start = r.j_start = 0;
+            continue;
+        }
+        bp.push_back(Bp {p, r.i_end, r.j_end, movTotal});
+        movTotal += r.i_end + r.j_end;
+    }
+    if (!bp.empty())
+    {
+        hipError_t e = hipSuccess;
+        const size_t nb = bp.size();
+        inf.batch_pairs = (int32_t)nb;
+        int sr;
+        if ((sr = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
+            (sr = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(gsa::OverlapWalkRec), 4096)) != GSA_SUCCESS)
+            return sr;
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        gsa::OverlapWalkRec* const drec = ctx->buf[kBufPairBatchRec].as<gsa::OverlapWalkRec>();
+        unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
+        const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+        std::vector<gsa::OverlapWalkRec> rec(nb);
+        std::memset(rec.data(), 0, nb * sizeof(gsa::OverlapWalkRec));
+        std::vector<gsa::OverlapBatchPairState> state(nb);
+        for (size_t b = 0; b < nb; ++b)
+        {
+            rec[b].i = (int)bp[b].iEnd;
+            rec[b].j = (int)bp[b].jEnd;
+            rec[b].state = 4u;
+            state[b].tHi = gsa::overlap_end_strip(TR, bp[b].iEnd);
+            state[b].J = bp[b].jEnd;
+            inf.strips += (int32_t)(state[b].tHi + 1);
+        }
+        if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(gsa::OverlapWalkRec), hipMemcpyHostToDevice, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        std::vector<gsa::OverlapBatchChunk> chunks;
+        std::vector<gsa::PairBatchTask> tasks;
+        std::vector<gsa::PairBatchDesc> descs;
+        std::vector<gsa::OverlapBatchWalk> walks;
+        std::vector<char> blob;
+        for (;;)
+        {
+            const long long used = gsa::overlap_batch_plan_round(TR, limit, state, &chunks);
+            if (chunks.empty())
+            {
+                for (const gsa::OverlapBatchPairState& s : state)
+                    if (s.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
+                break;
+            }
+            int s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096);
+            if (s != GSA_SUCCESS) return s;
+            unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
+            tasks.clear();
+            descs.clear();
+            walks.clear();
+            for (size_t c = 0; c < chunks.size(); ++c)
+            {
+                const gsa::OverlapBatchChunk& ch = chunks[c];
+                const Bp& B = bp[(size_t)ch.pair];
+                const gsa_pair_dev& P = pairs[B.p];
+                gsa::PairBatchDesc d;
+                std::memset(&d, 0, sizeof(d));
+                d.seqY = P.seqY;
+                d.seqX = P.seqX;
+                d.R = P.adjrows - 1;
+                d.iEnd = (int)B.iEnd;
+                d.J = (int)ch.c.J;  // the chunk's last column
+                d.granBase = route.granOff[(size_t)B.p];
+                d.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
+                d.stripBytes = ch.c.stripBytes;
+                descs.push_back(d);
+                for (long long t = ch.c.tLo; t <= ch.c.tHi; ++t)
+                {
+                    gsa::PairBatchTask k;
+                    k.pair = (int)c;
+                    k.strip = (int)t;
+                    k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, t);
+                    tasks.push_back(k);
+                }
+                gsa::OverlapBatchWalk w;
+                std::memset(&w, 0, sizeof(w));
+                w.seqY = P.seqY;
+                w.seqX = P.seqX;
+                w.codes = dcodes + ch.codeOff;
+                w.stripBytes = ch.c.stripBytes;
+                w.tLo = (int)ch.c.tLo;
+                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
+                w.rec = ch.pair;
+                w.moves = dmoves + B.movOff;
+                walks.push_back(w);
+            }
+            // the longest chains first
+            std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
+                return chunks[(size_t)a.pair].c.J > chunks[(size_t)b.pair].c.J;
+            });
+            // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
+            const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
+                         oWalk = oDesc + descs.size() * sizeof(gsa::PairBatchDesc),
+                         tabBytes = oWalk + walks.size() * sizeof(gsa::OverlapBatchWalk);
+            if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
+            char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
+            blob.assign(tabBytes, 0);
+            std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
+            std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(gsa::PairBatchDesc));
+            std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(gsa::OverlapBatchWalk));
+            if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            gsa::OverlapBatchFillArgs f;
+            std::memset(&f, 0, sizeof(f));
+            f.pairs = (const gsa::PairBatchDesc*)(dtab + oDesc);
+            f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
+            f.ntasks = (int)tasks.size();
+            f.subst = subst;
+            f.substsz = substsz;
+            f.go = gapo;
+            f.ge = gape;
+            f.gran = dgran;
+            f.gran2 = dgran + route.granTotal;
+            f.codes = dcodes;
+            f.counter = (unsigned*)dtab;
+            gsa::OverlapBatchWalkArgs w;
+            std::memset(&w, 0, sizeof(w));
+            w.walks = (const gsa::OverlapBatchWalk*)(dtab + oWalk);
+            w.nwalks = (int)walks.size();
+            w.krShift = KR == 8 ? 3 : 4;
+            w.recs = drec;
+            int grid = 1;
+            const int walkGrid = max_workgroups > 0 ? std::min(w.nwalks, (int)max_workgroups) : w.nwalks;
+            if ((e = gsa::overlap_batch_fill_grid(gapo != gape, KR, f.ntasks, max_workgroups, &grid)) != hipSuccess ||
+                (e = gsa::launch_overlap_batch_trace(f, w, KR, grid, walkGrid, ctx->adbev, st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            note_launch(ctx);
+            if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(gsa::OverlapWalkRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                (e = hipStreamSynchronize(st)) != hipSuccess)
+                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+            float m0 = 0.f, m1 = 0.f;
+            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+            inf.fill_ms += m0;
+            inf.walk_ms += m1;
+            inf.rounds += 1;
+            inf.strips_filled += (int32_t)tasks.size();
+            inf.code_bytes = std::max<int64_t>(inf.code_bytes, used);
+            // every record that came back: in range, and done on a free border or on its chunk's upper
+            // boundary right of column 0
+            for (const gsa::OverlapBatchChunk& ch : chunks)
+            {
+                const Bp& B = bp[(size_t)ch.pair];
+                const gsa::OverlapWalkRec& r = rec[(size_t)ch.pair];
+                if (r.n < 0 || r.n > B.iEnd + B.jEnd || r.i < 0 || r.i > B.iEnd || r.j < 0 || r.j > ch.c.J)
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+                if (!gsa::overlap_batch_advance(TR, ch.c, r.i, r.j, r.done != 0, &state[(size_t)ch.pair]))
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            }
+        }
+        std::vector<unsigned char> mv((size_t)movTotal + 1);
+        if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        for (size_t b = 0; b < nb; ++b)
+        {
+            gsa_align_db_result& r = res[(size_t)bp[b].p];
+            if (rec[b].i != 0 && rec[b].j != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            cig[(size_t)bp[b].p] = fold_cigar(mv.data() + bp[b].movOff, rec[b].n);
+            r.i_start = rec[b].i;
+            r.j_start = rec[b].j;
+            r.status = 0;
+        }
+    }
+    // the strings back to back in pair order; a pair's offset does not depend on the buffer's size
+    int64_t at = 0;
+    for (int p = 0; p < npairs; ++p)
+    {
+        gsa_align_db_result& r = res[(size_t)p];
+        const int64_t len = (int64_t)cig[(size_t)p].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+        out[p] = r;
+    }
+    if (cigar_need) *cigar_need = at;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                                int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
+                                gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                gsa_align_batch_overlap_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_batch_overlap_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, max_workgroups, scratch_limit, out, cigar,
+                                    cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_overlap_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                                int32_t gapo, int32_t gape, gsa_score_result* out, float* batch_kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_overlap_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, false, out, batch_kernel_ms,
+                                    pick_stream(ctx, stream));
+}
 
 int gsa_align_batch_semi_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                              int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,

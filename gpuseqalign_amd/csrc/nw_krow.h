@@ -86,5 +86,15 @@ hipError_t launch_overlap_max(const int* rowR, const int* colC, int R, int C, in
 hipError_t launch_krow_score_semi_batch(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
 hipError_t launch_semi_rowmax_batch(const PairDesc* pairs, int nPairs, int go, int ge, const unsigned* err, ScoreOut* out,
                                     hipStream_t stream);
+// Overlap scores of a batch of independent pairs (nw_kscore_overlap_batch.hip): launch_krow_score_semi_batch's
+// contract in the modes kModeScoreOV / OVL; pair p's row R goes to PairDesc::score as there, and column C
+// of every row of every one of its tickets to PairDesc::hcol[row], its own buffer of 1 + nTickets x
+// (256 k) ints at a multiple of 16 ints (rows past R are stored too, so a buffer sized by R alone would
+// be overwritten by its neighbour's last ticket).  launch_overlap_max_batch, enqueued behind it, takes
+// every pair's maximum as launch_overlap_max does, one workgroup per pair: out[p] = {score, i_end,
+// j_end, 0}, out[nPairs].score the error word *err (launch_score_finalize's layout).
+hipError_t launch_krow_score_overlap_batch(const StripArgs& a, int mode, int k, int grid, hipStream_t stream);
+hipError_t launch_overlap_max_batch(const PairDesc* pairs, int nPairs, int go, int ge, const unsigned* err, ScoreOut* out,
+                                    hipStream_t stream);
 
 }  // namespace gsa

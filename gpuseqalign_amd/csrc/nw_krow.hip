@@ -2545,6 +2545,12 @@ __global__ void __launch_bounds__(64 * kr_waves<kKrowNSDefault>()) nw_kscore_ker
             pa.tapGran = 0;
             // semi-global: the pair's own row buffer (score launches do not use PairDesc::score otherwise)
             if constexpr (is_sg_mode(MODE)) pa.rowR = d.score;
+            // overlap: the pair's own row and column buffers (nor do score launches use PairDesc::hcol)
+            if constexpr (is_ov_mode(MODE))
+            {
+                pa.rowR = d.score;
+                pa.tapH = d.hcol;
+            }
         }
         else if (h == 1)
         {
@@ -2748,6 +2754,79 @@ hipError_t launch_krow_score_semi(const StripArgs& a, int mode, int k, int grid,
 hipError_t launch_semi_rowmax(const int* rowR, int R, int C, int go, int ge, int* score, int* jend, hipStream_t stream)
 {
     hipLaunchKernelGGL(nw_semi_rowmax_kernel, dim3(1), dim3(kRowMaxThreads), 0, stream, rowR, R, C, go - ge, go, ge, score, jend);
+    return hipGetLastError();
+}
+#elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_OVERLAP_BATCH)
+// the overlap modes over a batch of independent pairs (nw_kscore_overlap_batch.hip: its own translation
+// unit, default scheduler): the BATCH instances, K = 2 and 4, int16 and int8 profiles
+namespace {
+
+constexpr int kOvMaxThreads = 1024;
+
+// nw_overlap_max_kernel (nw_kscore_overlap.hip) per pair, one workgroup each: R, C, row R (PairDesc::
+// score) and column C (PairDesc::hcol) from the pair's descriptor, the same key and tie rule -- the
+// largest value; at equal value a cell of row R, there the smallest j; otherwise the smallest i; the
+// analytic H(R, 0) = H(0, C) = 0 among the candidates.  out[p] = {score, i_end, j_end, 0} as
+// launch_score_finalize lays it out, out[nPairs] the launch's error word.
+__global__ void __launch_bounds__(kOvMaxThreads) nw_overlap_max_batch_kernel(const PairDesc* pairs, int nPairs, int dd, int ge,
+                                                                             const unsigned* err, ScoreOut* out)
+{
+    __shared__ long long sk[kOvMaxThreads];
+    auto key = [](int v, bool onRow, int idx) {
+        return (long long)(((unsigned long long)(uint32_t)v << 32) | (onRow ? 0x80000000u : 0u) | (0x7fffffffu & ~(uint32_t)idx));
+    };
+    const int p = blockIdx.x;
+    if (p >= nPairs) return;
+    const int R = pairs[p].R, C = pairs[p].C;
+    const int* const row = pairs[p].score;
+    const int* const col = pairs[p].hcol;
+    long long best = max(key(0, true, 0), key(0, false, 0));
+    for (int j = 1 + (int)threadIdx.x; j <= C; j += kOvMaxThreads)
+        best = max(best, key(row[kTapPad + j] - dd + (R + j) * ge, true, j));
+    for (int i = 1 + (int)threadIdx.x; i <= R; i += kOvMaxThreads) best = max(best, key(col[i] - dd + (i + C) * ge, false, i));
+    sk[threadIdx.x] = best;
+    __syncthreads();
+    for (int n = kOvMaxThreads / 2; n > 0; n >>= 1)
+    {
+        if ((int)threadIdx.x < n) sk[threadIdx.x] = max(sk[threadIdx.x], sk[threadIdx.x + n]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+    {
+        const uint32_t lo = (uint32_t)sk[0];
+        const bool onRow = (lo >> 31) != 0;
+        const int idx = (int)(0x7fffffffu & ~lo);
+        out[p] = ScoreOut {(int)(sk[0] >> 32), onRow ? R : idx, onRow ? idx : C, 0};
+        if (p == 0) out[nPairs] = ScoreOut {(int)err[0], 0, 0, 0};
+    }
+}
+
+}  // namespace
+
+hipError_t launch_krow_score_overlap_batch(const StripArgs& a, int mode, int k, int grid, hipStream_t stream)
+{
+    // independent pairs, every pair's row and column buffer in its descriptor; grid <= 0: every resident slot
+    if (!a.pairs || a.nPairs < 1 || a.bidiTop != 0 || a.bidiMid != 0 || a.tkFirst != 0 || a.tapRow != 0 || a.tapGran != 0 ||
+        !a.swBest)
+        return hipErrorInvalidValue;
+    if (k == 2)
+    {
+        if (mode == kModeScoreOV) return launch_ksq<kModeScoreOV, 2, true>(a, grid, stream);
+        if (mode == kModeScoreOVL) return launch_ksq<kModeScoreOVL, 2, true>(a, grid, stream);
+        return hipErrorInvalidValue;
+    }
+    if (k != 4) return hipErrorInvalidValue;
+    if (mode == kModeScoreOV) return launch_ksq<kModeScoreOV, 4, true>(a, grid, stream);
+    if (mode == kModeScoreOVL) return launch_ksq<kModeScoreOVL, 4, true>(a, grid, stream);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_overlap_max_batch(const PairDesc* pairs, int nPairs, int go, int ge, const unsigned* err, ScoreOut* out,
+                                    hipStream_t stream)
+{
+    if (nPairs < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nw_overlap_max_batch_kernel, dim3((unsigned)nPairs), dim3(kOvMaxThreads), 0, stream, pairs, nPairs,
+                       go - ge, ge, err, out);
     return hipGetLastError();
 }
 #elif defined(GSA_KROW_SCORE) && defined(GSA_KSCORE_OVERLAP)

@@ -1021,6 +1021,98 @@ int gsa_align_pair_overlap_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrow
                                int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
                                int64_t* cigar_need, gsa_align_pair_overlap_info* info, float* kernel_ms, void* stream);
 
+/* Long pairs, overlap (dovetail) mode: scores and alignments of a batch in one call.
+ *
+ * gsa_score_overlap_batch_dev takes gsa_score_semi_batch_dev's arguments: pairs is a HOST array (only
+ * seqY, adjrows, seqX and adjcols are read; two entries may name the same buffers), out a host array
+ * of npairs results.  Synchronous.
+ * Semantics: out[p] is exactly what gsa_score_overlap_dev returns for pair p alone, with calc_kernel_ms
+ * 0, whatever the pair's position or neighbours in the list, the rows per lane and the profile width;
+ * *batch_kernel_ms (may be null) gets the hipEvent time of the launch.  Pairs with an empty side are
+ * answered on the host as there: score 0 at (R, 0).
+ * How: the batched overlap instances of the K-rows score kernel (nw_kscore_overlap_batch.hip) run all
+ * pairs' tickets in one launch, 4 rows per lane in both gap models (GSA_SCORE_K=2 forces 2), the int8
+ * profile for linear gaps only (GSA_KROW_Q8 = 0 / 2: int16 / int8 always), as gsa_score_semi_batch_dev
+ * chooses them.  Every pair's row R goes to its own part of one row buffer, 4 (C + 208) bytes rounded
+ * up to 64, and column C of every row of every one of its tickets to its own part of one column buffer,
+ * 4 (1 + TR ceil(R / TR)) bytes rounded up to 64 -- the rows past R are stored too, so the pair's last
+ * ticket counts whole.  One workgroup per pair takes the maximum over its row R, its column C and the
+ * analytic H(R, 0) = H(0, C) = 0 under gsa_score_overlap_dev's tie rule, and one copy brings all
+ * answers back.
+ * Memory: the checkpoint rows the launch keeps cost 16 bytes per column per ticket (of 256 K rows) per
+ * pair.  A batch whose buffers cannot be allocated returns the allocation error with nothing launched.
+ * All scratch is counted in gsa_mem_stats.
+ * The mode has no second path, so no pair is routed elsewhere: it is errorInvalidValue, before
+ * anything is enqueued, for everything gsa_score_semi_batch_dev rejects and when any one pair is a pair
+ * gsa_score_overlap_dev refuses (its four conditions); out is then left as it was.  The call adds no
+ * launch kind and no knob, leaves the record of gsa_last_launch and the fills' sticky error word alone,
+ * and reports kernel errors in the score kernels' own control word.  An end cell that lies neither on
+ * row R nor on column C is errorKernelFailure. */
+int gsa_score_overlap_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                                int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out,
+                                float* batch_kernel_ms, void* stream);
+
+typedef struct gsa_align_batch_overlap_info {  /* what the call ran; optional out-parameter */
+    int32_t batch_pairs;    /* pairs traced on the device */
+    int32_t host_pairs;     /* pairs answered on the host: an empty side, or score 0 at (R, 0) */
+    int32_t strip_rows;     /* TR: rows of a strip, the batched score kernel's ticket (1024; 512 with
+                               GSA_SCORE_K=2); 0: that kernel did not run */
+    int32_t strips;         /* strips that hold the rows 1 ... i_end, over the traced pairs */
+    int32_t strips_filled;  /* strips filled with move codes, over all rounds; less than strips when a
+                               walk reached column 0 below strip 0 */
+    int32_t rounds;         /* fill + walk launch pairs */
+    int64_t code_bytes;     /* peak bytes of move codes held at once */
+    int64_t gran_bytes;     /* bytes of checkpoint rows the score launch kept */
+    float score_ms, fill_ms, walk_ms; /* hipEvent time of the batched score launch, and of the fill and the walk
+                                         launches summed over the rounds */
+    int32_t pad0;
+} gsa_align_batch_overlap_info;
+
+/* The overlap alignments of npairs pairs traced on the device together: gsa_align_batch_semi_dev's
+ * arguments.  Synchronous.
+ * Semantics: out[p] is, field for field, what gsa_align_pair_overlap_dev returns for pair p alone --
+ * score, both cells and the CIGAR, the same recurrences, tie rules and stop on either free border --
+ * whatever the strip height, the round, the pair's position or neighbours in the list and
+ * max_workgroups.  The CIGAR buffer follows gsa_align_db_dev's rules as gsa_align_batch_dev states
+ * them: the strings back to back in pair order, NUL-terminated, a pair's offset independent of
+ * cigar_cap, status 2 for a string that does not fit, *cigar_need (may be null) the bytes all need.
+ * Pairs with an empty side, and pairs whose score is 0 at (R, 0), are answered on the host as the
+ * single call answers them: the cells (R, 0)-(R, 0) and an empty CIGAR.
+ * How: gsa_score_overlap_batch_dev's launch leaves, per pair, the bottom row of each ticket of TR rows
+ * in the pair's own hand-off rows; TR is 1024 (512 with GSA_SCORE_K=2), where gsa_align_pair_overlap_dev
+ * uses 512 for affine gaps.  A pair's strips run from the one that holds its i_end upwards -- an end
+ * cell on column C above row R leaves the strips below it alone -- and a strip's codes take
+ * j_end TR / 2 bytes: codes run from column 1, there is no column window.  The strips of many pairs are
+ * filled in one launch, one wave per strip, and the walks run side by side, one wave per pair
+ * (nw_pair_overlap_trace_batch.hip).  scratch_limit is the bytes of codes the call may hold at once; 0
+ * is the default, 8 GiB.  When the strips do not all fit the call runs rounds: the pairs are taken by
+ * remaining code bytes descending, ties by index; each gets its lowest unfilled strip and as many above
+ * it as still fit the round, for the columns 1 ... j where its walk stands; a pair for which nothing is
+ * left waits.  A pair whose walk stands on row 0 or on column 0 after a round is done, and the strips
+ * above the chunk in which it reached column 0 are not filled at all (info.strips_filled <
+ * info.strips).  A round is one upload of its tables, one fill launch, one walk launch and one small
+ * copy back.  max_workgroups caps the grid of the fill and of the walk (0: all resident).
+ * Memory: gsa_score_overlap_batch_dev's rule (info.gran_bytes); all scratch is counted in
+ * gsa_mem_stats.
+ * Status 1 -- score and end cell valid, start cell 0, an empty CIGAR -- for a pair one strip of whose
+ * codes (j_end TR / 2 bytes) exceeds scratch_limit.  The single call answers errorInvalidValue behind
+ * the score launch there; a batch must not lose every answer to one pair, so here the other pairs are
+ * unaffected.  The condition can differ from the single call's only through the strip height (1024
+ * here against 512 there for affine gaps), at a limit between the two strip sizes.
+ * The mode has no second path, so no pair is routed elsewhere: it is errorInvalidValue, before
+ * anything is enqueued, for everything gsa_score_overlap_batch_dev rejects, for any one pair that
+ * gsa_align_pair_overlap_dev would refuse (its value bound B of 2^26 or more included), for a negative
+ * scratch_limit, cigar_cap or max_workgroups, a null out, or a null cigar with cigar_cap > 0; out is
+ * then left as it was.  A record that comes back out of range, or a walk that stopped neither on a
+ * free border nor on its chunk's upper boundary, is errorKernelFailure.  *info (may be null) says what
+ * the call ran.  The call adds no launch kind and no knob and leaves the record of gsa_last_launch and
+ * the fills' sticky error word alone.  *kernel_ms (may be null) gets the hipEvent time of all kernels
+ * of the call. */
+int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                                int32_t substsz, int32_t gapo, int32_t gape, int32_t max_workgroups,
+                                int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                                int64_t* cigar_need, gsa_align_batch_overlap_info* info, float* kernel_ms, void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
