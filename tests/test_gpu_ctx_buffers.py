@@ -1,33 +1,19 @@
 """The context's grow-only buffers (csrc/gsa_ctx.h: Buf, reserve, StageRing) under growth: every entry
 point family on a fresh engine at a small shape, one several times larger and the small one again;
 the pinned staging rings wrapped with copies still in flight; glmem_peak_allocs over that growth; and
-contexts created and destroyed in a row.  Every output exactly against the oracles the other GPU
-tests use (oracle.fill_full, oracle.sparse_headers, oracle.trace_sparse, oracle.score_ag,
-tests/_align_oracle.py).  A fresh gsa.Engine(0) per test, not the session's, so that growth happens."""
+contexts created and destroyed in a row.  Every output exactly against the CPU references: the runners
+and their references are tests/_families.py's, one per entry-point family.  A fresh gsa.Engine(0) per
+test, not the session's, so that growth happens."""
 import numpy as np
 import pytest
 
 import gpuseqalign_amd as gsa
-import oracle
-from gpuseqalign_amd import formats as F
-from tests import _align_oracle as ao
-from tests._data import random_pair
+from tests import _families as fam
+from tests._families import BY_NAME, FAMILIES, G, LARGE, SMALL, TRACE_BX, _dev, _empty, _pair
 
 pytestmark = pytest.mark.gpu
 
-SMALL, LARGE = "small", "large"
 GROWTH = (SMALL, LARGE, SMALL)
-PAIR = {SMALL: (300, 250), LARGE: (3000, 2500)}
-TRIPLE = {SMALL: [(300, 250), (250, 300), (120, 280)], LARGE: [(3000, 2500), (2500, 3000), (1200, 2800)]}
-G = -11
-_REF = {}
-
-
-def _once(key, fn):
-    """A reference computed once and shared by the tests."""
-    if key not in _REF:
-        _REF[key] = fn()
-    return _REF[key]
 
 
 @pytest.fixture
@@ -47,77 +33,26 @@ def fresh():
         e.close()
 
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to("cuda:0")
-
-
-def _empty(n):
-    import torch
-    return torch.full((int(n),), -7, dtype=torch.int32, device="cuda:0")
-
-
-def _pair(R, C):
-    return random_pair(R, C, 11 * R + C)
-
-
-def _headers(R, C, tBx):
-    Y, X = _pair(R, C)
-    return _once(("hdr", R, C, tBx), lambda: oracle.sparse_headers(Y, X, _SUB[0], G, gsa.sparse_tile_by(), tBx))
-
-
-def _matrix(R, C):
-    Y, X = _pair(R, C)
-    return _once(("full", R, C), lambda: oracle.fill_full(Y, X, _SUB[0], G)[0])
-
-
-_SUB = []  # the table (golden.blosum62), set by the `sub` fixture
-
-
 @pytest.fixture
-def sub(golden):
-    if not _SUB:
-        _SUB.append(golden.blosum62)
-    return golden.blosum62
+def sub():
+    return fam.table()
 
 
 def _substsz(sub):
     return int(round(np.sqrt(np.asarray(sub).size)))
 
 
-# -- one call of each family at one size, checked -----------------------------------------------
-
-def _sparse_launch(e, sub, R, C, tBx, stream=None):
-    """fill_sparse_dev enqueued; (check, tensors kept alive)."""
+def _headers(R, C, tBx):
     Y, X = _pair(R, C)
-    geom = gsa.sparse_geometry(len(Y), len(X), tBx)
-    y, x, s = _dev(Y), _dev(X), _dev(sub)
-    hr, hc = _empty(geom.hrowElems), _empty(geom.hcolElems)
-    e.fill_sparse_dev(y.data_ptr(), len(Y), x.data_ptr(), len(X), s.data_ptr(), _substsz(sub), G, tBx, hr.data_ptr(),
-                      hc.data_ptr(), stream)
-    return (y, x, s, hr, hc), geom
+    return fam._once(("hdr", R, C, tBx), lambda: fam.headers(Y, X, fam.table(), tBx))
 
 
-def run_fill_sparse(e, sub, size):
-    R, C = PAIR[size]
-    (_, _, _, hr, hc), _ = _sparse_launch(e, sub, R, C, 64)
-    e.sync()
-    assert e.last_launch()["kind"] == "sparse_krow"
-    want = _headers(R, C, 64)
-    assert np.array_equal(hr.cpu().numpy(), want[0]) and np.array_equal(hc.cpu().numpy(), want[1]), (size, R, C)
-
-
-def run_fill_full(e, sub, size):
-    """A single pair: the fused two-pass fill."""
-    R, C = PAIR[size]
+def _matrix(R, C):
     Y, X = _pair(R, C)
-    y, x, s = _dev(Y), _dev(X), _dev(sub)
-    out = _empty(len(Y) * len(X))
-    e.fill_full_dev(y.data_ptr(), len(Y), x.data_ptr(), len(X), s.data_ptr(), _substsz(sub), G, out.data_ptr())
-    e.sync()
-    assert e.last_launch()["kind"] == "full_fused"
-    assert np.array_equal(out.cpu().numpy().reshape(len(Y), len(X)), _matrix(R, C)), (size, R, C)
+    return fam._once(("full", R, C), lambda: fam.matrix(Y, X, fam.table()))
 
+
+# -- one call of each family at one size, checked: tests/_families.py ---------------------------------
 
 def _full_batch_launch(e, sub, shapes, stream=None):
     pairs = [_pair(R, C) for R, C in shapes]
@@ -134,144 +69,13 @@ def _full_batch_check(shapes, outs, what):
         assert np.array_equal(o.cpu().numpy().reshape(R + 1, C + 1), _matrix(R, C)), (what, R, C)
 
 
-def run_fill_full_batch(e, sub, size):
-    """Three pairs: the two-pass fill in two launches, its expansion scratch and staging."""
-    keep, outs = _full_batch_launch(e, sub, TRIPLE[size])
-    e.sync()
-    assert e.last_launch()["kind"] == "full_two_launch"
-    _full_batch_check(TRIPLE[size], outs, size)
-
-
-def _run_score(e, sub, size, knob, kind, both_ends=0):
-    R, C = PAIR[size]
-    Y, X = _pair(R, C)
-    y, x, s = _dev(Y), _dev(X), _dev(sub)
-    if knob:
-        e.set_knob(*knob)
-    for go, ge, local in [(-11, -1, False), (-11, -11, True)]:
-        r = e.score_dev(y.data_ptr(), len(Y), x.data_ptr(), len(X), s.data_ptr(), _substsz(sub), go, ge, local)
-        ll = e.last_launch()
-        assert ll["kind"] == kind, ll
-        if not local:  # (a local pair may come back from both ends to one direction)
-            assert ll["both_ends"] == both_ends, ll
-        want = _once(("score", R, C, go, ge, local), lambda: oracle.score_ag(Y, X, sub, go, ge, local))
-        assert (r["score"], r["i_end"], r["j_end"]) == want, (size, go, ge, local)
-
-
-def run_score(e, sub, size):
-    _run_score(e, sub, size, None, "score_krow")
-
-
-def run_score_both_ends(e, sub, size):
-    """GSA_SCORE_BIDI=2: from both ends at any size (the tap rows and reversed sequences' buffer)."""
-    _run_score(e, sub, size, ("GSA_SCORE_BIDI", "2"), "score_krow", both_ends=1)
-
-
-def run_score_scan(e, sub, size):
-    """GSA_SCORE_SCAN=1: the row scan and its boundary rows."""
-    _run_score(e, sub, size, ("GSA_SCORE_SCAN", "1"), "score_scan")
-
-
-def run_score_batch(e, sub, size):
-    shapes = TRIPLE[size]
-    pairs = [_pair(R, C) for R, C in shapes]
-    s = _dev(sub)
-    ins = [(_dev(Y), _dev(X)) for Y, X in pairs]
-    ptrs = [(y.data_ptr(), y.numel(), x.data_ptr(), x.numel()) for y, x in ins]
-    for go, ge, local in [(-11, -1, False), (-11, -11, True)]:
-        res = e.score_batch_dev(ptrs, s.data_ptr(), _substsz(sub), go, ge, local)
-        assert e.last_launch()["kind"] == "score_krow" and e.last_launch()["npairs"] == 3
-        for (R, C), (Y, X), r in zip(shapes, pairs, res):
-            want = _once(("score", R, C, go, ge, local), lambda: oracle.score_ag(Y, X, sub, go, ge, local))
-            assert (r["score"], r["i_end"], r["j_end"]) == want, (size, R, C, go, ge, local)
-
-
-def _sweep_rows(e, sub):
-    """Query rows one sweep of the database lane kernel covers (score_db_impl: passes = ceil(R /
-    kDbLanesPassRows), 16 lanes of gsa_last_launch's k rows each); a longer query needs the
-    boundary-row buffer."""
-    if "sweep" not in _REF:
-        q, x, s = _dev(F.synthetic_seq(5, 1)), _dev(F.synthetic_seq(7, 2)), _dev(sub)
-        e.score_db_dev(q.data_ptr(), q.numel(), x.data_ptr(), [0, x.numel()], s.data_ptr(), _substsz(sub), -11, -1, False)
-        ll = e.last_launch()
-        assert ll["kind"] == "score_lanes", ll
-        _REF["sweep"] = 16 * ll["k"]
-    return _REF["sweep"]
-
-
-def run_db(e, sub, size):
-    """score_db_dev and align_db_dev: the small query fits one sweep (no boundary rows), the large one
-    takes three."""
-    sweep = _sweep_rows(e, sub)
-    R = {SMALL: sweep - 84, LARGE: 2 * sweep + 5}[size]
-    n, lo, hi = {SMALL: (9, 1, 80), LARGE: (150, 200, 700)}[size]
-    rng = np.random.default_rng(R)
-    query = F.synthetic_seq(R, 900 + R)
-    subjects = [F.synthetic_seq(int(c), 1000 * R + i) for i, c in enumerate(rng.integers(lo, hi + 1, n))]
-    q, db, s = _dev(query), _dev(np.concatenate(subjects)), _dev(sub)
-    off = np.concatenate([[0], np.cumsum([len(x) for x in subjects])]).astype(np.int64)
-    hits = list(range(0, n, max(1, n // 6)))
-    for go, ge, local in [(-11, -1, False), (-11, -11, True)]:
-        res = e.score_db_dev(q.data_ptr(), q.numel(), db.data_ptr(), off, s.data_ptr(), _substsz(sub), go, ge, local)
-        ll = e.last_launch()
-        assert ll["kind"] == "score_lanes" and ll["npairs"] == n, ll
-        for k, (X, r) in enumerate(zip(subjects, res)):
-            want = _once(("db", R, k, go, ge, local), lambda: oracle.score_ag(query, X, sub, go, ge, local))
-            assert (r["score"], r["i_end"], r["j_end"]) == want, (size, k, go, ge, local)
-        al = e.align_db_dev(q.data_ptr(), q.numel(), db.data_ptr(), off, hits, s.data_ptr(), _substsz(sub), go, ge, local)
-        info = e.last_align_db_info()
-        assert info["lane_hits"] == len(hits) and info["unsupported"] == 0 and info["chunks"] == 1, info
-        for h, r in zip(hits, al):
-            want = _once(("adb", R, h, go, ge, local), lambda: ao.align(query, subjects[h], sub, go, ge, local))
-            assert r["status"] == 0
-            assert tuple(r[f] for f in ("score", "i_start", "j_start", "i_end", "j_end", "cigar")) == want, (size, h)
-
-
-TRACE_BX = 1024  # a tile too wide for its move codes to sit in LDS (dirs_lds false): they stay in global memory
-
-
-def run_trace_sparse(e, sub, size):
-    R, C = PAIR[size]
-    Y, X = _pair(R, C)
-    (y, x, s, hr, hc), geom = _sparse_launch(e, sub, R, C, TRACE_BX)
-    e.sync()
-    got = e.trace_sparse_dev(y.data_ptr(), len(Y), x.data_ptr(), len(X), s.data_ptr(), _substsz(sub), G, geom,
-                             hr.data_ptr(), hc.data_ptr())
-    ll = e.last_launch()
-    assert ll["kind"] == "trace_sparse", ll
-    h = _headers(R, C, TRACE_BX)
-    want = _once(("trace", R, C), lambda: oracle.trace_sparse(h[0], h[1], h[2], h[3], gsa.sparse_tile_by(), TRACE_BX,
-                                                              Y, X, sub, G))
-    assert got == want, (size, R, C)
-
-
-def _run_align_sparse(e, sub, size, overlap):
-    R, C = PAIR[size]
-    Y, X = _pair(R, C)
-    r = e.align_sparse(Y, X, sub, G, tileBx=64, overlap=overlap)
-    want = _headers(R, C, 64)
-    assert np.array_equal(r.hrow, want[0]) and np.array_equal(r.hcol, want[1]) and r.align_cost == want[4], (size, R, C)
-
-
-def run_align_sparse(e, sub, size):
-    _run_align_sparse(e, sub, size, False)
-
-
-def run_align_sparse_pt(e, sub, size):
-    _run_align_sparse(e, sub, size, True)
-
-
-FAMILIES = [run_fill_sparse, run_fill_full, run_fill_full_batch, run_score, run_score_both_ends, run_score_scan,
-            run_score_batch, run_db, run_trace_sparse, run_align_sparse, run_align_sparse_pt]
-
-
-@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: f.__name__[4:])
-def test_grow_shrink_regrow(fresh, sub, family):
+@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: f.name)
+def test_grow_shrink_regrow(fresh, family):
     """Small, then several times larger (every buffer of the family regrows), then small again (in the
     larger buffers): all three results exact."""
     e = fresh()
     for size in GROWTH:
-        family(e, sub, size)
+        family.run(e, size)
 
 
 def test_trace_tile_keeps_codes_in_global_memory():
@@ -327,25 +131,25 @@ def test_staging_ring_wraps_full(fresh, sub):
 
 # -- accounting ----------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("family", [run_fill_sparse, run_fill_full, run_fill_full_batch, run_score_batch],
-                         ids=lambda f: f.__name__[4:])
-def test_peak_allocs_follow_the_capacity_held(fresh, sub, family):
+@pytest.mark.parametrize("family", [BY_NAME[n] for n in ("fill_sparse", "fill_full", "fill_full_batch", "score_batch")],
+                         ids=lambda f: f.name)
+def test_peak_allocs_follow_the_capacity_held(fresh, family):
     """glmem_peak_allocs is the device capacity held at a launch: a repeated call allocates nothing, a
     larger one raises it, and buffers never shrink."""
     e = fresh()
     peak = lambda: e.mem_stats()["glmem_peak_allocs"]
     e.reset_mem_stats()
-    family(e, sub, SMALL)
+    family.run(e, SMALL)
     p1 = peak()
     assert p1 > 0
-    family(e, sub, SMALL)
+    family.run(e, SMALL)
     assert peak() == p1
-    family(e, sub, LARGE)
+    family.run(e, LARGE)
     p2 = peak()
     assert p2 > p1
     e.reset_mem_stats()
     assert peak() == 0
-    family(e, sub, SMALL)
+    family.run(e, SMALL)
     assert peak() >= p2
 
 
@@ -358,11 +162,9 @@ def test_create_use_destroy_in_a_row(fresh, sub):
         e = gsa.Engine(0)
         try:
             for family in FAMILIES:
-                family(e, sub, SMALL)
-                e.set_knob("GSA_SCORE_BIDI", None)
-                e.set_knob("GSA_SCORE_SCAN", None)
+                family.run(e, SMALL)  # (a runner unsets the knob it set)
         finally:
             e.close()
     e = fresh()
-    run_fill_sparse(e, sub, SMALL)
-    run_fill_full(e, sub, SMALL)
+    BY_NAME["fill_sparse"].run(e, SMALL)
+    BY_NAME["fill_full"].run(e, SMALL)
