@@ -325,6 +325,15 @@ SIGNATURES = {
                                                    ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
                                                    ctypes.POINTER(_i64), ctypes.POINTER(AlignDbMultiInfo),
                                                    ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_db_multi_overlap_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64),
+                                                      _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32p,
+                                                      ctypes.POINTER(DbHit), ctypes.POINTER(ScoreDbMultiInfo),
+                                                      ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_db_multi_overlap_dev": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), _i32, _vp, ctypes.POINTER(_i64),
+                                                      _i32, _i32p, _i32p, _i32, _vp, _i32, _i32, _i32, _i32, _i64,
+                                                      ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                                      ctypes.POINTER(_i64), ctypes.POINTER(AlignDbMultiInfo),
+                                                      ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score":(ctypes.c_int, [_vp, _i32p, _i32, _i32p, _i32, _i32p, _i32, _i32, _i32, _i32,
                                  ctypes.POINTER(ScoreResult), ctypes.POINTER(_Laps)]),
     "gsa_trace_sparse_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, ctypes.POINTER(SparseGeom),
@@ -1251,7 +1260,7 @@ class Engine:
 
     def _score_db_many(self, entry: str, queries_ptr, q_off, db_ptr, db_off, subst_ptr, substsz, gapo, gape, mode: tuple,
                        top, want_scores, max_workgroups, scratch_limit, stream):
-        """The call behind score_db_multi_dev (mode = (local,)) and score_db_semi_dev (mode = ()):
+        """The call behind score_db_multi_dev (mode = (local,)), score_db_semi_dev and score_db_overlap_dev (mode = ()):
         (result dict, info dict)."""
         qo = np.ascontiguousarray(q_off, dtype=np.int64)
         off = np.ascontiguousarray(db_off, dtype=np.int64)
@@ -1309,7 +1318,7 @@ class Engine:
 
     def _align_db_many(self, entry: str, queries_ptr, q_off, db_ptr, db_off, hit_query, hit_subject, subst_ptr, substsz,
                        gapo, gape, mode: tuple, max_workgroups, scratch_limit, stream):
-        """The call behind align_db_multi_dev (mode = (local,)) and align_db_semi_dev (mode = ()):
+        """The call behind align_db_multi_dev (mode = (local,)), align_db_semi_dev and align_db_overlap_dev (mode = ()):
         (list of result dicts, info dict)."""
         qo = np.ascontiguousarray(q_off, dtype=np.int64)
         off = np.ascontiguousarray(db_off, dtype=np.int64)
@@ -1471,6 +1480,84 @@ class Engine:
         hq = np.repeat(np.arange(hits.shape[0], dtype=np.int32), hits.shape[1])
         hs = np.ascontiguousarray(hits["subject"], dtype=np.int32).ravel()
         res = self.align_db_semi_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hq, hs, dS.data_ptr(), substsz, gapo, gape)
+        ntop = hits.shape[1]
+        return [list(zip([int(x) for x in hs[q * ntop:(q + 1) * ntop]], res[q * ntop:(q + 1) * ntop]))
+                for q in range(hits.shape[0])]
+
+    # -- overlap (dovetail) database search: all four overhangs free ------
+
+    def score_db_overlap_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, subst_ptr: int, substsz: int,
+                             gapo: int, gape: Optional[int] = None, top: int = 0, want_scores: bool = True,
+                             max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None) -> dict:
+        """Many queries against a database in the overlap (dovetail) shape
+        (gsa_score_db_multi_overlap_dev; synchronous): a suffix of either sequence on a prefix of the
+        other, or either within the other.  Arguments and result as score_db_semi_dev's; a hit's
+        (i_end, j_end) is (R, the smallest column of row R that attains the score) if row R attains
+        it, else (the smallest such row, C), and scores are never negative.  The mode has no second
+        path: a pair the lane kernels cannot take makes the call errorInvalidValue (include/gsa.h).
+        last_score_db_overlap_info() says what ran."""
+        res, self._score_db_overlap_info = self._score_db_many(
+            "gsa_score_db_multi_overlap_dev", queries_ptr, q_off, db_ptr, db_off, subst_ptr, substsz, gapo, gape, (), top,
+            want_scores, max_workgroups, scratch_limit, stream)
+        return res
+
+    def last_score_db_overlap_info(self) -> dict:
+        """gsa_score_db_multi_info of the last score_db_overlap_dev call on this engine (the keys of
+        last_score_db_multi_info(); "other_queries" is 0)."""
+        info = getattr(self, "_score_db_overlap_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_score_db_overlap_info: no score_db_overlap_dev call yet")
+        return dict(info)
+
+    def score_db_overlap(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, top: int = 0) -> dict:
+        """score_db_overlap_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front, as score_db_multi takes them."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.score_db_overlap_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape, top)
+
+    def align_db_overlap_dev(self, queries_ptr: int, q_off, db_ptr: int, db_off, hit_query, hit_subject, subst_ptr: int,
+                             substsz: int, gapo: int, gape: Optional[int] = None, max_workgroups: int = 0,
+                             scratch_limit: int = 0, stream: Optional[int] = None) -> list:
+        """The overlap alignments of chosen (query, subject) pairs (gsa_align_db_multi_overlap_dev;
+        synchronous): arguments and result dicts as align_db_semi_dev's.  Score and end cell are
+        score_db_overlap_dev's; the walk stops on row 0 or column 0, so one of "i_start" and
+        "j_start" is 0 and the CIGAR covers the overlap alone.  Status is never 1: what the kernels
+        cannot take makes the call errorInvalidValue.  last_align_db_overlap_info() says what the
+        call ran."""
+        res, self._align_db_overlap_info = self._align_db_many(
+            "gsa_align_db_multi_overlap_dev", queries_ptr, q_off, db_ptr, db_off, hit_query, hit_subject, subst_ptr,
+            substsz, gapo, gape, (), max_workgroups, scratch_limit, stream)
+        return res
+
+    def last_align_db_overlap_info(self) -> dict:
+        """gsa_align_db_multi_info of the last align_db_overlap_dev call on this engine (the keys of
+        last_align_db_multi_info(); "unsupported" is 0)."""
+        info = getattr(self, "_align_db_overlap_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_db_overlap_info: no align_db_overlap_dev call yet")
+        return dict(info)
+
+    def align_db_overlap(self, queries, subjects, hit_query, hit_subject, subst, gapo: int,
+                         gape: Optional[int] = None) -> list:
+        """align_db_overlap_dev over host arrays: every entry of `queries` and of `subjects` with the
+        header element in front; `hit_query` indexes `queries`, `hit_subject` indexes `subjects`."""
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        return self.align_db_overlap_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hit_query, hit_subject, dS.data_ptr(),
+                                         substsz, gapo, gape)
+
+    def search_db_overlap(self, queries, subjects, subst, gapo: int, gape: Optional[int] = None, top: int = 10) -> list:
+        """Overlap database search with alignments for many queries: one upload, one
+        score_db_overlap_dev with `top` and one align_db_overlap_dev on all the hits.  Per query
+        [(subject_index, result dict)], best subject first."""
+        if max(int(top), 0) == 0:
+            return [[] for _ in queries]
+        dQ, qoff, dD, off, dS, substsz = self._pack_db_multi(queries, subjects, subst)
+        hits = self.score_db_overlap_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, dS.data_ptr(), substsz, gapo, gape, top,
+                                         want_scores=False)["hits"]
+        hq = np.repeat(np.arange(hits.shape[0], dtype=np.int32), hits.shape[1])
+        hs = np.ascontiguousarray(hits["subject"], dtype=np.int32).ravel()
+        res = self.align_db_overlap_dev(dQ.data_ptr(), qoff, dD.data_ptr(), off, hq, hs, dS.data_ptr(), substsz, gapo,
+                                        gape)
         ntop = hits.shape[1]
         return [list(zip([int(x) for x in hs[q * ntop:(q + 1) * ntop]], res[q * ntop:(q + 1) * ntop]))
                 for q in range(hits.shape[0])]

@@ -21,6 +21,8 @@
 #include "nw_lanes_multi.h"
 #include "nw_lanes_semi.h"
 #include "nw_lanes_semi_trace.h"
+#include "nw_lanes_overlap.h"
+#include "nw_lanes_overlap_trace.h"
 #include "nw_lanes_trace.h"
 #include "nw_lanes_trace_multi.h"
 #include "nw_pair_semi_plan.h"
@@ -1358,6 +1360,31 @@ int semi_ranges(const gsa_ctx* ctx, int64_t R, int64_t C, long long smax, int32_
     return GSA_SUCCESS;
 }
 
+// The alignment shape of a database call: the two old modes (global or local, by `local`), semi-global
+//  or overlap (2.2o).  The last two have the lane kernels and no second path.
+enum class DbShape
+{
+    plain,
+    semi,
+    overlap
+};
+
+// The overlap calls: semi_ranges' three tests, and a query of at most 8191 letters,
+// because the end cell's row travels in a key beside the value as its column does (with a small table
+// the LDS test alone lets longer queries through).  All grow with R and with C.
+int overlap_ranges(const gsa_ctx* ctx, int64_t R, int64_t C, long long smax, int32_t substsz, int32_t gapo, int32_t gape)
+{
+    if (R > gsa::kDbOverlapMaxR) return GSA_ERROR_INVALID_VALUE;
+    return semi_ranges(ctx, R, C, smax, substsz, gapo, gape);
+}
+
+int lane_only_ranges(DbShape shape, const gsa_ctx* ctx, int64_t R, int64_t C, long long smax, int32_t substsz, int32_t gapo,
+                     int32_t gape)
+{
+    return shape == DbShape::overlap ? overlap_ranges(ctx, R, C, smax, substsz, gapo, gape)
+                                     : semi_ranges(ctx, R, C, smax, substsz, gapo, gape);
+}
+
 // Default of gsa_score_db_multi_dev's scratch_limit: bytes of result matrix a call holds at once.
 constexpr int64_t kDbMultiScratch = 256ll << 20;
 
@@ -1377,13 +1404,17 @@ bool offsets_ok(const int64_t* off, int32_t n)
 // semi (gsa_score_db_multi_semi_dev, local = 0): the semi-global shape of nw_lanes_semi.hip.  There is
 // no other path for it: every pair with letters on both sides runs on the lane kernel or the call is
 // refused before anything is enqueued, and GSA_DB_LANES / GSA_DB_MAXC are not read.
+// overlap (gsa_score_db_multi_overlap_dev, local = 0): the overlap shape of nw_lanes_overlap.hip, routed
+// as the semi-global one is, with overlap_ranges' tests.
 int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                         const int64_t* db_off, int32_t nsubj, const int32_t* subst, int32_t substsz, int32_t gapo,
-                        int32_t gape, int32_t local, bool semi, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                        int32_t gape, int32_t local, DbShape shape, int32_t top, int32_t max_workgroups, int64_t scratch_limit,
                         int32_t* scores, gsa_db_hit* hits, gsa_score_db_multi_info* info, float* kernel_ms,
                         hipStream_t st)
 {
     static_assert(sizeof(gsa_db_hit) == sizeof(gsa::DbMultiHit), "gsa_db_hit is the ranking's record");
+    const bool overlap = shape == DbShape::overlap;
+    const bool semi = shape != DbShape::plain;  // the lane kernels alone, no second path
     if (!ctx || !queries || !q_off || !db || !db_off || !subst) return GSA_ERROR_INVALID_VALUE;
     if (nq < 1 || nsubj < 1) return GSA_ERROR_INVALID_VALUE;
     if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
@@ -1421,7 +1452,7 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         // score_ranges' bounds grow with R and with C: the longest query against the longest subject
         // is outside every kernel's range iff any pair is
         bool stripOk = false;
-        const int s = semi ? semi_ranges(ctx, Rmax, Cmax, smax, substsz, gapo, gape)
+        const int s = semi ? lane_only_ranges(shape, ctx, Rmax, Cmax, smax, substsz, gapo, gape)
                            : score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
         if (s != GSA_SUCCESS) return s;
     }
@@ -1451,6 +1482,8 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
     auto empty_pair = [&](int64_t R, int64_t C) {
         const int64_t k = R + C;
         // semi-global: no query letters, score 0 at (0, 0); no subject letters, R inserts ending in (R, 0)
+        // overlap: an empty side, score 0 at (R, 0)
+        if (overlap) return gsa::DbLanesOut {0, (int)R, 0, 0};
         if (semi) return gsa::DbLanesOut {R == 0 ? 0 : (int)(gapo + (R - 1) * gape), (int)R, 0, 0};
         return gsa::DbLanesOut {(local || k == 0) ? 0 : (int)(gapo + (k - 1) * gape), local ? 0 : (int)R, local ? 0 : (int)C, 0};
     };
@@ -1578,8 +1611,9 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             const int passes = passes_of(hq[b].R);
             while (k < hq.size() && passes_of(hq[k].R) == passes) ++k;
             int wgs = 1;
-            if ((e = semi ? gsa::dbsemi_resident(passes, substsz, gapo != gape, &wgs)
-                          : gsa::dbmulti_resident(passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+            if ((e = overlap ? gsa::dboverlap_resident(passes, substsz, gapo != gape, &wgs)
+                     : semi  ? gsa::dbsemi_resident(passes, substsz, gapo != gape, &wgs)
+                             : gsa::dbmulti_resident(passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             const long long nunits = (long long)(k - b) * unitsPerQuery;
             int grid = (int)std::max<long long>(1, std::min<long long>(wgs, nunits));
@@ -1620,7 +1654,9 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             a.bnd = a.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
             a.bndStride = cmax + 1;
             if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            if ((e = semi ? gsa::launch_dbsemi(a, grids[c], st) : gsa::launch_dbmulti(a, local, grids[c], st)) != hipSuccess)
+            if ((e = overlap ? gsa::launch_dboverlap(a, grids[c], st)
+                     : semi  ? gsa::launch_dbsemi(a, grids[c], st)
+                             : gsa::launch_dbmulti(a, local, grids[c], st)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             note_launch(ctx);
             inf.launches += 1;
@@ -1682,14 +1718,18 @@ int score_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
 // semi (gsa_align_db_multi_semi_dev, local = 0): the semi-global shape of nw_lanes_semi_trace.hip on
 // the same plan and buffers.  No hit is status 1: a hit outside semi_ranges, or a scratch_limit below
 // the largest hit's move codes, refuses the call before anything is enqueued.
+// overlap (gsa_align_db_multi_overlap_dev, local = 0): the overlap shape of nw_lanes_overlap_trace.hip,
+// routed as the semi-global one is, with overlap_ranges' tests over the hits.
 int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq, const int32_t* db,
                         const int64_t* db_off, int32_t nsubj, const int32_t* hit_query, const int32_t* hit_subject,
                         int32_t nhits, const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
-                        bool semi, int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                        DbShape shape, int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
                         int64_t cigar_cap, int64_t* cigar_need, gsa_align_db_multi_info* info, float* kernel_ms,
                         hipStream_t st)
 {
     if (!ctx || !queries || !q_off || !db || !db_off || !subst || !out) return GSA_ERROR_INVALID_VALUE;
+    const bool overlap = shape == DbShape::overlap;
+    const bool semi = shape != DbShape::plain;  // the lane kernels alone, no second path
     if (nq < 1 || nsubj < 1) return GSA_ERROR_INVALID_VALUE;
     if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
     if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
@@ -1722,7 +1762,7 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         // score_ranges' bounds grow with R and with C: the longest query against the longest subject
         // is outside every kernel's range iff any pair is
         bool stripOk = false;
-        // (semi-global: the hits alone are tested, below)
+        // (semi-global and overlap: the hits alone are tested, below)
         const int s = semi ? GSA_SUCCESS : score_ranges(Rmax, Cmax, smax, gapo, gape, local, &stripOk);
         if (s != GSA_SUCCESS) return s;
     }
@@ -1739,6 +1779,12 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         const int64_t R = rows_of(hit_query[h]), C = cols_of(hit_subject[h]);
         gsa_align_db_result& r = out[h];
         std::memset(&r, 0, sizeof(r));
+        if (overlap && (R == 0 || C == 0))
+        {
+            // an empty side: score 0, all cells (R, 0), nothing to say
+            r.i_start = r.i_end = R;
+            continue;
+        }
         if (semi && (R == 0 || C == 0))
         {
             // no query letters: score 0 at (0, 0), nothing to say; no subject letters: R inserts
@@ -1752,7 +1798,7 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         }
         if (semi)
         {
-            if (semi_ranges(ctx, R, C, smax, substsz, gapo, gape) != GSA_SUCCESS || gsa::dbtrace_code_bytes(R, C) > limit)
+            if (lane_only_ranges(shape, ctx, R, C, smax, substsz, gapo, gape) != GSA_SUCCESS || gsa::dbtrace_code_bytes(R, C) > limit)
                 return GSA_ERROR_INVALID_VALUE;
             lane[(size_t)h] = 1;
             continue;
@@ -1800,8 +1846,9 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             for (const gsa::DbaLaunch& L : ch.launches)
             {
                 int wgs = 1;
-                if ((e = semi ? gsa::dbsemi_trace_resident(L.passes, substsz, gapo != gape, &wgs)
-                              : gsa::dbtrace_multi_resident(L.passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
+                if ((e = overlap ? gsa::dboverlap_trace_resident(L.passes, substsz, gapo != gape, &wgs)
+                         : semi  ? gsa::dbsemi_trace_resident(L.passes, substsz, gapo != gape, &wgs)
+                                 : gsa::dbtrace_multi_resident(L.passes, substsz, local, gapo != gape, &wgs)) != hipSuccess)
                     return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
                 int grid = std::max(1, std::min(wgs, L.nunits));
                 if (max_workgroups > 0) grid = std::min(grid, max_workgroups);
@@ -1881,8 +1928,9 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
                 a.bnd = L.passes > 1 ? ctx->buf[kBufDbbnd].as<int2>() : nullptr;
                 a.bndStride = ch.cmax + 1;
                 if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                if ((e = semi ? gsa::launch_dbsemi_trace_fill(a, grids[c][l], st)
-                              : gsa::launch_dbtrace_multi_fill(a, local, grids[c][l], st)) != hipSuccess)
+                if ((e = overlap ? gsa::launch_dboverlap_trace_fill(a, grids[c][l], st)
+                         : semi  ? gsa::launch_dbsemi_trace_fill(a, grids[c][l], st)
+                                 : gsa::launch_dbtrace_multi_fill(a, local, grids[c][l], st)) != hipSuccess)
                     return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
                 note_launch(ctx);
                 inf.launches += 1;
@@ -1904,7 +1952,9 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             w.moveOff = (const long long*)(meta + moffAt);
             w.res = (gsa::DbTraceOut*)adbres;
             w.moves = adbres + movAt;
-            if ((e = semi ? gsa::launch_dbsemi_trace_walk(w, st) : gsa::launch_dbtrace_multi_walk(w, st)) != hipSuccess)
+            if ((e = overlap ? gsa::launch_dboverlap_trace_walk(w, st)
+                     : semi  ? gsa::launch_dbsemi_trace_walk(w, st)
+                             : gsa::launch_dbtrace_multi_walk(w, st)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
             (void)hipEventRecord(ctx->adbev[2], st);
             if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)ch.moveBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
@@ -4065,8 +4115,8 @@ int gsa_align_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
-                               gapo, gape, local, false, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need,
-                               info, kernel_ms, pick_stream(ctx, stream));
+                               gapo, gape, local, DbShape::plain, max_workgroups, scratch_limit, out, cigar, cigar_cap,
+                               cigar_need, info, kernel_ms, pick_stream(ctx, stream));
 }
 
 int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
@@ -4078,8 +4128,21 @@ int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int6
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
-                               gapo, gape, 0, true, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need, info,
-                               kernel_ms, pick_stream(ctx, stream));
+                               gapo, gape, 0, DbShape::semi, max_workgroups, scratch_limit, out, cigar, cigar_cap, cigar_need,
+                               info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_db_multi_overlap_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                   const int32_t* db, const int64_t* db_off, int32_t nsubj, const int32_t* hit_query,
+                                   const int32_t* hit_subject, int32_t nhits, const int32_t* subst, int32_t substsz,
+                                   int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
+                                   gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                   gsa_align_db_multi_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return align_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, hit_query, hit_subject, nhits, subst, substsz,
+                               gapo, gape, 0, DbShape::overlap, max_workgroups, scratch_limit, out, cigar, cigar_cap,
+                               cigar_need, info, kernel_ms, pick_stream(ctx, stream));
 }
 
 int32_t gsa_align_db_multi_unit(void) { return gsa::kDbAlignMultiUnit; }
@@ -4091,8 +4154,8 @@ int gsa_score_db_multi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* 
                            void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, local, false, top,
-                               max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, local, DbShape::plain,
+                               top, max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
 }
 
 int gsa_score_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
@@ -4102,8 +4165,19 @@ int gsa_score_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int6
                                 float* kernel_ms, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, 0, true, top,
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, 0, DbShape::semi, top,
                                max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_db_multi_overlap_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                   const int32_t* db, const int64_t* db_off, int32_t nsubj, const int32_t* subst,
+                                   int32_t substsz, int32_t gapo, int32_t gape, int32_t top, int32_t max_workgroups,
+                                   int64_t scratch_limit, int32_t* scores, gsa_db_hit* hits,
+                                   gsa_score_db_multi_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return score_db_multi_impl(ctx, queries, q_off, nq, db, db_off, nsubj, subst, substsz, gapo, gape, 0, DbShape::overlap,
+                               top, max_workgroups, scratch_limit, scores, hits, info, kernel_ms, pick_stream(ctx, stream));
 }
 
 int32_t gsa_score_db_multi_unit(void) { return gsa::kDbMultiUnit; }

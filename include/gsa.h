@@ -773,6 +773,71 @@ int gsa_align_db_multi_semi_dev(gsa_ctx* ctx, const int32_t* queries, const int6
                                 int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
                                 char* cigar, int64_t cigar_cap, int64_t* cigar_need,
                                 gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
+
+/* Database search, overlap (dovetail) mode: a suffix of either sequence on a prefix of the other, or
+ * either within the other.
+ * The alignment shape of "Long pairs, overlap (dovetail) mode" below (gsa_score_overlap_dev), word for
+ * word, per (query, subject) pair: an adapter that runs off a read's 3' end, a primer hanging over an
+ * amplicon's end, the overlaps of a few thousand short reads, all against all.  The query has R letters
+ * down the rows, the subject C letters along the columns, gapo <= gape <= 0, and
+ *   row 0 and column 0 are free: H = 0, E = F = minus infinity;
+ *   inside, the Gotoh recurrences of "score-only NW / SW" above, without the zero floor;
+ *   candidates: the cells of row R (j = 0 ... C) and of column C (i = 0 ... R);
+ *   score = the largest H among the candidates, so never negative: H(R, 0) = 0 is one;
+ *   end cell: (R, the SMALLEST j that attains the score) if row R attains it, otherwise
+ *   (the SMALLEST such i, C); a score of 0 therefore ends at (R, 0), and the corner (R, C) counts as
+ *   row R.
+ * A pair with an empty side has score 0 and end cell (R, 0), answered on the host.
+ *
+ * gsa_score_db_multi_overlap_dev takes gsa_score_db_multi_semi_dev's arguments, and they mean what they
+ * mean there: result rows {score, i_end, j_end} per (query, subject), the same chunks of result rows
+ * by scratch_limit, the same ranking by (score descending, subject index ascending) on the device,
+ * top, scores, hits, *info (a gsa_score_db_multi_info with other_queries = 0), *kernel_ms and the same
+ * device buffers, counted in gsa_mem_stats; no new buffer slot.  The pairs run on
+ * nw_lanes_overlap.hip, one persistent launch per sweep class with gsa_score_db_multi_unit() tasks
+ * per unit.
+ * This mode has no second path: a pair runs on the lane kernels or the call is refused.  It is
+ * errorInvalidValue, before anything is enqueued, when any (query, subject) pair with letters on both
+ * sides has a subject of more than 8191 letters; a query of more than 8191 letters (the end cell's row
+ * index travels in a key beside the value, as the column index does; with a small table the LDS test
+ * alone would let longer queries through); a query whose profile (4 substsz (384 ceil(R / 384) + 4)
+ * bytes) does not fit the LDS a workgroup may have; or a value bound
+ * B = smax min(R, C) + |gapo| + (R + C) |gape| >= 2^18 (smax: the largest |table value|).  As all four
+ * grow with R and C, the longest query against the longest subject decides.  GSA_DB_MAXC and
+ * GSA_DB_LANES do not apply.  Everything gsa_score_db_multi_semi_dev rejects is rejected here too.  The
+ * call adds no launch kind and no knob: the record of gsa_last_launch is left untouched and the fills'
+ * sticky error word is left alone. */
+int gsa_score_db_multi_overlap_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                   const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                                   int32_t top, int32_t max_workgroups, int64_t scratch_limit,
+                                   int32_t* scores, gsa_db_hit* hits,
+                                   gsa_score_db_multi_info* info, float* kernel_ms, void* stream);
+
+/* The overlap alignments of nhits (query, subject) pairs, traced on the device: the arguments of
+ * gsa_align_db_multi_semi_dev, the same result struct, CIGAR buffer rules (strings back to back in hit
+ * order, status 2 for one that does not fit, *cigar_need), chunks by scratch_limit (0: 256 MiB), *info
+ * and *kernel_ms.
+ * Semantics: score and end cell are gsa_score_db_multi_overlap_dev's for the pair.  The walk goes
+ * backwards from the end cell in state H under gsa_align_db_dev's rules -- diagonal before F before E
+ * at equal value, a gap extended only when that is strictly better than opening -- and stops as soon
+ * as i = 0 or j = 0: (i_start, j_start) is the cell it stopped in, and nothing is emitted along a
+ * border, so all four overhangs stay out of the CIGAR.  A score of 0 has start = end = (R, 0) and an
+ * empty CIGAR; so has a pair with an empty side, on the host.
+ * No hit is status 1 (info->unsupported = 0): the call is errorInvalidValue, before anything is
+ * enqueued, when a hit with letters on both sides fails one of gsa_score_db_multi_overlap_dev's four
+ * tests (evaluated over the hits only), or when scratch_limit is below the largest hit's move codes
+ * (192 ceil(R / 384) (C + 1) bytes).  Everything gsa_align_db_multi_semi_dev rejects is rejected here
+ * too.  The fill and the walk are nw_lanes_overlap_trace.hip's on gsa_align_db_multi_dev's plan and
+ * buffers.  The call adds no launch kind and no knob and leaves the record of gsa_last_launch
+ * untouched. */
+int gsa_align_db_multi_overlap_dev(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_off, int32_t nq,
+                                   const int32_t* db, const int64_t* db_off, int32_t nsubj,
+                                   const int32_t* hit_query, const int32_t* hit_subject, int32_t nhits,
+                                   const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape,
+                                   int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out,
+                                   char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                   gsa_align_db_multi_info* info, float* kernel_ms, void* stream);
 /* Long pairs, semi-global mode: a whole query within one long subject.
  * The alignment shape of "Database search, semi-global mode" above, word for word, for one pair of any
  * length the K-rows score kernel takes (a read against a contig): seqY is the query (R letters, down
