@@ -156,6 +156,14 @@ class AlignPairOverlapInfo(ctypes.Structure):
                 ("pad0", ctypes.c_int32)]
 
 
+class AlignPairBandInfo(ctypes.Structure):
+    """gsa_align_pair_band_info (include/gsa.h): what the last gsa_align_pair_band_dev call ran."""
+    _fields_ = [("strip_rows", ctypes.c_int32), ("strips", ctypes.c_int32), ("waves", ctypes.c_int32),
+                ("supersteps", ctypes.c_int32), ("proved_optimal", ctypes.c_int32), ("pad0", ctypes.c_int32),
+                ("band_lo", ctypes.c_int64), ("band_hi", ctypes.c_int64), ("code_bytes", ctypes.c_int64),
+                ("score_ms", ctypes.c_float), ("walk_ms", ctypes.c_float)]
+
+
 class AlignBatchInfo(ctypes.Structure):
     """gsa_align_batch_info (include/gsa.h): what the last gsa_align_batch_dev call ran."""
     _fields_ = [("batch_pairs", ctypes.c_int32), ("alone_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32),
@@ -281,6 +289,12 @@ SIGNATURES = {
                                                   ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
                                                   ctypes.POINTER(_i64), ctypes.POINTER(AlignPairOverlapInfo),
                                                   ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_band_max_width": (ctypes.c_int64, []),
+    "gsa_score_band_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64,
+                                          ctypes.POINTER(ScoreResult), _vp]),
+    "gsa_align_pair_band_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _i64,
+                                               ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                               ctypes.POINTER(AlignPairBandInfo), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
@@ -388,6 +402,11 @@ def _c32(a) -> np.ndarray:
 def score_db_multi_unit() -> int:
     """Wave tasks (of four subjects) in a unit of gsa_score_db_multi_dev."""
     return int(lib().gsa_score_db_multi_unit())
+
+
+def band_max_width() -> int:
+    """Most diagonals a band of score_band / align_pair_band may hold after clamping."""
+    return int(lib().gsa_band_max_width())
 
 
 def align_db_multi_unit() -> int:
@@ -801,6 +820,101 @@ class Engine:
         torch.cuda.synchronize(dev)
         return self.align_pair_overlap_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
                                            gapo, gape, scratch_limit)
+
+    # -- long pairs, banded: global alignment inside a band of diagonals --
+    def score_band_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int, substsz: int,
+                       gapo: int, gape: Optional[int], band_lo: int, band_hi: int, stream: Optional[int] = None) -> dict:
+        """Banded global score of one device-resident pair (gsa_score_band_dev; synchronous): only the
+        cells with band_lo <= j - i <= band_hi exist.  The arguments of score_semi_dev, with the band
+        behind gape (None: gapo).  {"score", "i_end", "j_end", "kernel_ms"}; the end cell is (R, C).
+        The band must hold (0, 0) and (R, C) and, clamped to the matrix, at most band_max_width()
+        diagonals."""
+        r = ScoreResult()
+        st = lib().gsa_score_band_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                      gapo if gape is None else gape, int(band_lo), int(band_hi), ctypes.byref(r), stream)
+        self._check(st, "gsa_score_band_dev")
+        return {"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end),
+                "kernel_ms": float(r.calc_kernel_ms)}
+
+    @staticmethod
+    def _band_of(R: int, C: int, band_lo, band_hi, band):
+        """The band of the host forms: (band_lo, band_hi) as given, or `band` diagonals on either side
+        of the ones that (0, 0) and (R, C) need.  Exactly one of the two forms."""
+        pair = band_lo is not None or band_hi is not None
+        if pair == (band is not None) or (pair and (band_lo is None or band_hi is None)):
+            raise ValueError("give either band_lo and band_hi, or band")
+        if pair:
+            return int(band_lo), int(band_hi)
+        return min(0, C - R) - int(band), max(0, C - R) + int(band)
+
+    def score_band(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None, band_lo: Optional[int] = None,
+                   band_hi: Optional[int] = None, band: Optional[int] = None) -> dict:
+        """score_band_dev over host arrays: the sequences with the header element in front, as score()
+        takes them.  The band as (band_lo, band_hi), or band=k for band_lo = min(0, C - R) - k and
+        band_hi = max(0, C - R) + k; exactly one of the two forms, else ValueError."""
+        import torch
+        lo, hi = self._band_of(len(seqY) - 1, len(seqX) - 1, band_lo, band_hi, band)
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return self.score_band_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz, gapo,
+                                   gape, lo, hi)
+
+    def align_pair_band_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int,
+                            substsz: int, gapo: int, gape: Optional[int], band_lo: int, band_hi: int,
+                            scratch_limit: int = 0, stream: Optional[int] = None) -> dict:
+        """The banded global alignment of one device-resident pair (gsa_align_pair_band_dev;
+        synchronous): the arguments of score_band_dev, and `scratch_limit`, the bytes of move codes the
+        call may hold (0: the default, 2 GiB).  {"score", "status", "i_start", "j_start", "i_end",
+        "j_end", "cigar", "kernel_ms"} as align_pair_dev returns them, from (0, 0) to (R, C); status 1:
+        score and end cell only (the value bound reaches 2^26, or the codes exceed scratch_limit).
+        last_align_pair_band_info() says what ran, and whether the result is proved to be the unbanded
+        one."""
+        res = AlignDbResult()
+        info = AlignPairBandInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes always suffice
+        cap = 2 * (max(adjrows - 1, 0) + max(adjcols - 1, 0)) + 1
+        buf = ctypes.create_string_buffer(cap)
+        st = lib().gsa_align_pair_band_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                           gapo if gape is None else gape, int(band_lo), int(band_hi),
+                                           int(scratch_limit), ctypes.byref(res), buf, cap, ctypes.byref(need),
+                                           ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_pair_band_dev")
+        self._align_pair_band_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                      for k, t in info._fields_ if k != "pad0"}
+        cig = buf.raw[res.cigar_off:res.cigar_off + res.cigar_len].decode() if res.status == 0 else ""
+        return {"score": int(res.score), "status": int(res.status), "i_start": int(res.i_start),
+                "j_start": int(res.j_start), "i_end": int(res.i_end), "j_end": int(res.j_end), "cigar": cig,
+                "kernel_ms": float(ms.value)}
+
+    def last_align_pair_band_info(self) -> dict:
+        """gsa_align_pair_band_info of the last align_pair_band_dev call on this engine: "strip_rows",
+        "strips", "waves", "supersteps" (the workgroup's barriers), "proved_optimal" (1: the result is
+        the unbanded call's, field for field), "band_lo" and "band_hi" (clamped to the matrix),
+        "code_bytes", "score_ms" (the fill) and "walk_ms"."""
+        info = getattr(self, "_align_pair_band_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_pair_band_info: no align_pair_band_dev call yet")
+        return dict(info)
+
+    def align_pair_band(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None, band_lo: Optional[int] = None,
+                        band_hi: Optional[int] = None, band: Optional[int] = None, scratch_limit: int = 0) -> dict:
+        """align_pair_band_dev over host arrays, with the band as score_band() takes it."""
+        import torch
+        lo, hi = self._band_of(len(seqY) - 1, len(seqX) - 1, band_lo, band_hi, band)
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        substsz = int(round(np.sqrt(subst.size)))
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return self.align_pair_band_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
+                                        gapo, gape, lo, hi, scratch_limit)
 
     def score_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
                         local: bool = False, stream: Optional[int] = None) -> list:

@@ -2,7 +2,8 @@
 // gsa_score, gsa_score_dev, gsa_score_batch_dev, gsa_score_db_dev, gsa_score_db_multi_dev,
 // gsa_align_db_dev, gsa_align_db_multi_dev, gsa_align_pair_dev and gsa_align_batch_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
 // (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
-// nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip).  The context
+// nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip); the banded calls
+// gsa_score_band_dev and gsa_align_pair_band_dev on nw_band.hip.  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 
 #include "../../include/gsa.h"
 #include "gsa_ctx.h"
+#include "nw_band.h"
 #include "nw_bidi.h"
 #include "nw_krow.h"
 #include "nw_lanes.h"
@@ -4010,9 +4012,198 @@ int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
     return GSA_SUCCESS;
 }
 
+// gsa_score_band_dev and gsa_align_pair_band_dev (align: the latter): the checks, the plan
+// (nw_band_plan.h), one fill launch of one workgroup -- with move codes when the alignment is wanted
+// and the 4 v + tag form and scratch_limit take them -- and, with codes, the walk; one copy brings the
+// score and the walk's record back, a second the move bytes.  The certificate is computed here.
+// Scratch: kBufPairMeta ([0] the result words, [64] the walk's record, [128] the pair's descriptor),
+// kBufPairCodes, kBufPairMoves.  gsa_last_launch's record is not touched.
+int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols, const int32_t* subst,
+              int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo, int64_t band_hi, bool align, int64_t scratch_limit,
+              gsa_score_result* sout, gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+              gsa_align_pair_band_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || !seqY || !seqX || !subst || (align ? !out : !sout)) return GSA_ERROR_INVALID_VALUE;
+    int s = check_inputs(adjrows, adjcols, substsz);
+    if (s != GSA_SUCCESS) return s;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (align && (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar))) return GSA_ERROR_INVALID_VALUE;
+    const int64_t R = adjrows - 1, C = adjcols - 1;
+    if (R >= (1ll << 30) || C >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;  // the kernel's int32 cell indices
+    if (!gsa::band_valid(R, C, band_lo, band_hi)) return GSA_ERROR_INVALID_VALUE;
+    gsa::band_clamp(R, C, &band_lo, &band_hi);
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_pair_band_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    inf.band_lo = band_lo;
+    inf.band_hi = band_hi;
+    gsa_align_db_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.i_end = R;
+    r.j_end = C;
+    std::string cig;
+    if (R == 0 || C == 0)
+    {
+        // one boundary, answered on the host: row 0 is E only, column 0 F only; no path leaves the band.  The
+        // one gap run is held to gsa_score_dev's value range (no table value takes part: smax = 1)
+        const int64_t k = R + C;
+        bool stripOk = false;
+        if (k > 0 && (s = score_ranges(R, C, 1, gapo, gape, 0, &stripOk)) != GSA_SUCCESS) return s;
+        if (k > 0)
+        {
+            r.score = (int32_t)(gapo + (k - 1) * gape);
+            cig = std::to_string(k) + (R > 0 ? 'I' : 'D');
+        }
+        inf.proved_optimal = 1;
+    }
+    else
+    {
+        gsa::BandPlan plan;
+        if (!gsa::band_plan(R, C, band_lo, band_hi, &plan)) return GSA_ERROR_INVALID_VALUE;  // wider than the limit
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        const long long smax = subst_absmax(sub.data(), substsz);
+        const long long pmax = std::max<long long>(0, *std::max_element(sub.begin(), sub.end()));
+        bool stripOk = false;
+        if ((s = score_ranges(R, C, smax, gapo, gape, 0, &stripOk)) != GSA_SUCCESS) return s;
+        // the fill with codes keeps 4 x value + source: |H| <= B (score_ranges' bound, which holds in the band)
+        const bool valOk = smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+        const int64_t limit = scratch_limit > 0 ? scratch_limit : gsa::kBandScratch;
+        const bool codes = align && valOk && plan.codeBytes <= limit;
+        inf.strip_rows = gsa::kBandTR;
+        inf.strips = (int32_t)plan.strips;
+        inf.waves = plan.waves;
+        inf.supersteps = (int32_t)plan.T;
+        inf.code_bytes = plan.codeBytes;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS) return s;
+        if (codes && ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)plan.codeBytes, 4096)) != GSA_SUCCESS ||
+                      (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(R + C), 4096)) != GSA_SUCCESS))
+            return s;
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        char* const meta = ctx->buf[kBufPairMeta].as<char>();
+        gsa::BandWalkRec* const drec = (gsa::BandWalkRec*)(meta + 64);
+        gsa::BandDesc* const ddesc = (gsa::BandDesc*)(meta + 128);
+        static_assert(sizeof(gsa::BandWalkRec) <= 64 && sizeof(gsa::BandDesc) <= 128, "the slots of kBufPairMeta");
+        gsa::BandDesc d;
+        std::memset(&d, 0, sizeof(d));
+        d.seqY = seqY;
+        d.seqX = seqX;
+        d.codes = codes ? ctx->buf[kBufPairCodes].as<unsigned char>() : nullptr;
+        d.result = (int*)meta;
+        d.stripBytes = plan.stripBytes;
+        d.R = (int)R;
+        d.C = (int)C;
+        d.lo = (int)plan.lo;
+        d.hi = (int)plan.hi;
+        d.strips = (int)plan.strips;
+        d.nq = (int)plan.nq;
+        d.T = (int)plan.T;
+        d.Wc = (int)plan.Wc;
+        gsa::BandWalkArgs w;
+        std::memset(&w, 0, sizeof(w));
+        w.seqY = seqY;
+        w.seqX = seqX;
+        w.codes = d.codes;
+        w.stripBytes = plan.stripBytes;
+        w.R = d.R;
+        w.C = d.C;
+        w.lo = d.lo;
+        w.hi = d.hi;
+        w.rec = drec;
+        w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+        // the result words and the walk's record start from zero: a kernel that wrote nothing is seen
+        if ((e = hipMemsetAsync(meta, 0, 128, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(ddesc, &d, sizeof(d), hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        if ((e = gsa::launch_band(ddesc, 1, plan.waves, subst, substsz, gapo, gape, codes, codes ? &w : nullptr, ctx->adbev,
+                                  st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        struct
+        {
+            int res[16];
+            gsa::BandWalkRec rec;
+        } back;
+        static_assert(sizeof(back) == 64 + sizeof(gsa::BandWalkRec), "the first two slots of kBufPairMeta");
+        if ((e = hipMemcpyAsync(&back, meta, sizeof(back), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        (void)hipEventElapsedTime(&inf.score_ms, ctx->adbev[0], ctx->adbev[1]);
+        if (codes) (void)hipEventElapsedTime(&inf.walk_ms, ctx->adbev[1], ctx->adbev[2]);
+        if (back.res[1] != 1) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+        r.score = back.res[0];
+        r.status = codes ? 0 : 1;
+        if (codes)
+        {
+            const gsa::BandWalkRec& rec = back.rec;
+            // a step off the band, a record out of range, or a walk that did not end at (0, 0)
+            if (rec.offband || !rec.done || rec.n < 0 || rec.n > R + C || rec.i != 0 || rec.j != 0)
+                return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            std::vector<unsigned char> mv((size_t)rec.n + 1);
+            if (rec.n > 0 &&
+                ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+                 (e = hipStreamSynchronize(st)) != hipSuccess))
+                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+            cig = fold_cigar(mv.data(), rec.n);
+        }
+        inf.proved_optimal = gsa::band_certificate(R, C, plan.lo, plan.hi, pmax, gapo, gape, r.score);
+    }
+    if (!align)
+    {
+        sout->score = r.score;
+        sout->i_end = R;
+        sout->j_end = C;
+        sout->calc_kernel_ms = inf.score_ms;
+        return GSA_SUCCESS;
+    }
+    if (r.status == 0)
+    {
+        const int64_t len = (int64_t)cig.size();
+        if (len + 1 <= cigar_cap)
+        {
+            std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
+            r.cigar_len = len;
+        }
+        else
+            r.status = 2;
+        if (cigar_need) *cigar_need = len + 1;
+    }
+    *out = r;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t gsa_band_max_width(void) { return gsa::kBandMaxWidth; }
+
+int gsa_score_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo, int64_t band_hi,
+                       gsa_score_result* out, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, false, 0, out, nullptr,
+                     nullptr, 0, nullptr, nullptr, nullptr, pick_stream(ctx, stream));
+}
+
+int gsa_align_pair_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo, int64_t band_hi,
+                            int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                            gsa_align_pair_band_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, true, scratch_limit,
+                     nullptr, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
 
 int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                                 int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,

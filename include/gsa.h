@@ -1178,6 +1178,103 @@ int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev
                                 int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
                                 int64_t* cigar_need, gsa_align_batch_overlap_info* info, float* kernel_ms, void* stream);
 
+/* Long pairs, banded: score and alignment of one pair inside a diagonal band.
+ * For two related long sequences -- two assemblies of one locus, a corrected read against its
+ * reference window, two haplotypes -- almost all of the R x C rectangle cannot hold the alignment.
+ * These two calls fill a band of diagonals only, and write the move codes in the same pass.
+ *
+ * Semantics.  seqY is the query, R letters, down the rows.  seqX is the subject, C letters, along the
+ * columns.  Both carry the header element in front.  gapo <= gape <= 0.
+ * The band is a pair band_lo <= band_hi of diagonals j - i.  Cell (i, j), 0 <= i <= R, 0 <= j <= C, is
+ * in the band iff band_lo <= j - i <= band_hi.
+ *   Every cell outside the band has H = E = F = minus infinity, border cells included.
+ *   Inside the band: gsa_align_pair_dev's global recurrences, borders, tie rule and CIGAR letters.
+ *     H(0, 0) = 0.
+ *     Row 0: H = E = go + (j - 1) ge, F = minus infinity.
+ *     Column 0: H = F = go + (i - 1) ge, E = minus infinity.
+ *     Walk from (R, C) in state H: diagonal before F before E.
+ *     A gap is extended only when that is strictly better than opening.
+ *     Row 0 is E only, column 0 is F only.
+ *   Results: score = H(R, C); end cell (R, C), start cell (0, 0); the CIGAR of that walk, which by
+ *   construction never leaves the band.
+ *   Validity: band_lo <= min(0, C - R) and band_hi >= max(0, C - R), else errorInvalidValue, since no
+ *   alignment exists.  The call clamps band_lo to -R and band_hi to C.  Wider changes nothing.  The
+ *   info struct reports the clamped values.
+ *   W = band_hi - band_lo + 1 after clamping must be at most a compile-time limit, which
+ *   gsa_band_max_width() returns (5826: nw_band_plan.h derives it from the waves' schedule).  Beyond
+ *   it the call is errorInvalidValue: the unbanded calls are the tool for bands that wide.
+ *   R = 0 or C = 0 are answered on the host: all-D or all-I, under the same validity rule and
+ *   gsa_score_dev's value range for the one gap run (the width limit does not apply there: nothing is
+ *   launched).
+ *   Minus infinity is any finite value that never wins.  Every in-band cell is reachable from (0, 0)
+ *   inside the band, so a real H exists at every in-band cell.  E / F values derived from minus
+ *   infinity are one step deep and never accumulate.
+ * The certificate (proved_optimal).  Let pmax = max(0, largest table value), D = C - R, S the banded
+ * score, and band_lo, band_hi the clamped values.
+ *   A path that leaves the band on the high side has at least band_hi + 1 letters of D and
+ *   band_hi + 1 - D of I.  So it scores at most
+ *     U_hi = pmax (C - band_hi - 1) + 2 gapo + band_hi gape + (band_hi - D) gape.
+ *   This applies only if band_hi < C.
+ *   On the low side, with a = 1 - band_lo, a path scores at most
+ *     U_lo = pmax (R - a) + 2 gapo + (a - 1) gape + (a + D - 1) gape.
+ *   This applies only if band_lo > -R.
+ *   proved_optimal = 1 iff S is strictly greater than every bound that applies.
+ *   Then every optimal unbanded alignment lies in the band, and the call's six fields and CIGAR are
+ *   exactly those of gsa_align_pair_dev for the same pair (global).  Strictness is what makes ties safe.
+ *
+ * How (nw_band.hip): one workgroup of min(16, strips) waves.  Strip s holds the rows s TR + 1 ...
+ * (s + 1) TR (TR = 256, 4 rows per lane) and sweeps only the W + TR - 1 columns from its own origin
+ * s TR + 1 + band_lo.  The waves run in lockstep super-steps of 64 columns with one workgroup barrier
+ * between them; strip s starts at super-step 6 s on wave s mod 16 and takes the row above it from a
+ * ring in LDS that strip s - 1 filled in strictly earlier super-steps.  Nothing polls memory.  The
+ * alignment call stores the 4-bit move codes of the band in that one pass, strips x (W + TR - 1) x
+ * TR / 2 bytes in all, and one lane walks them; there are no checkpoint rows, no refill and no chunks.
+ * One workgroup is a sliver of the chip: the calls pay when the band is a small part of the
+ * rectangle (DESIGN.md 2.2p has the measurements).
+ *
+ * Both calls are synchronous.  gsa_score_band_dev fills gsa_score_dev's result struct: score, end
+ * cell (R, C), the hipEvent time of the fill.  It runs the instance without move codes, on plain
+ * int32 values.  Refusals, all errorInvalidValue before anything is enqueued: everything gsa_score_dev
+ * rejects for a global pair, B + |gapo| < 2^29 included, with B = smax min(R, C) + |gapo| +
+ * (R + C) |gape| (inside the band every cell is reached by one gap and a diagonal run, so the same
+ * bound holds); R or C of 2^30 or more; the validity and width rules above; a null out.  The calls
+ * add no launch kind and no knob, leave the record of gsa_last_launch and the fills' sticky error
+ * word alone, and count their scratch in gsa_mem_stats. */
+int64_t gsa_band_max_width(void);
+int gsa_score_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                       const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo,
+                       int64_t band_hi, gsa_score_result* out, void* stream);
+
+typedef struct gsa_align_pair_band_info {  /* what the call ran; optional out-parameter */
+    int32_t strip_rows;      /* TR: rows of a strip (256) */
+    int32_t strips;          /* strips that hold the rows 1 ... R */
+    int32_t waves;           /* waves of the workgroup */
+    int32_t supersteps;      /* T: barriers of the workgroup, (strips - 1) lag + ceil((W + TR + 62) / 64) */
+    int32_t proved_optimal;  /* the certificate above */
+    int32_t pad0;
+    int64_t band_lo, band_hi; /* the clamped band */
+    int64_t code_bytes;      /* bytes of move codes of the band (also when they exceed scratch_limit) */
+    float score_ms, walk_ms; /* hipEvent time of the fill and of the walk */
+} gsa_align_pair_band_info;
+
+/* The banded alignment of one long pair, traced on the device: gsa_score_band_dev's arguments,
+ * gsa_align_pair_dev's result struct and CIGAR buffer rules (one NUL-terminated string at cigar[0],
+ * status 2 when it does not fit cigar_cap with the cells still valid, *cigar_need the bytes it needs,
+ * 2 (R + C) + 1 always enough).  scratch_limit is the bytes of move codes the call may hold; 0 is the
+ * default, 2 GiB.  Status 1 means score and end cell from the instance without codes and an empty
+ * CIGAR; it applies when B reaches 2^26 (the fill keeps 4 x value + source) or when code_bytes
+ * exceeds scratch_limit (info->code_bytes says what it would take).  The walk's record is validated
+ * on the host: at most R + C moves, ended at (0, 0); a step onto a cell outside the band is
+ * errorKernelFailure.  errorInvalidValue, before anything is enqueued, for everything
+ * gsa_score_band_dev refuses, a negative scratch_limit or cigar_cap and a null cigar with
+ * cigar_cap > 0.  *info (may be null) says what the call ran; *kernel_ms (may be null) gets the
+ * hipEvent time of both kernels. */
+int gsa_align_pair_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                            const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo,
+                            int64_t band_hi, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                            int64_t cigar_cap, int64_t* cigar_need, gsa_align_pair_band_info* info, float* kernel_ms,
+                            void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
