@@ -88,6 +88,7 @@ constexpr int kBlk = 16;          // steps per block
 constexpr int kHalo = kBlk / 4;   // halo registers (int4) per block
 constexpr int kRing = 512;        // hand-off ring elements per strip boundary (power of 2)
 constexpr int kBig = 0x3fffffff;  // "everything published"
+constexpr int kNoCap = 0x7fffffff;  // kr_strip: "no header column left to capture" as a block index
 constexpr int kSubRow = 36;       // dwords per subT row (32 letters + 4)
 constexpr int kBatch = 128;       // profile columns the loader adds per pass (2 per lane)
 // Progress words in 8-byte slots, slot s (s = -1 .. NS) at byte 8(s+1) = {prog[s+1], cons[s]}:
@@ -231,6 +232,12 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
     const uint32_t c_out = L.flags + kr_cons(w + 1);
     const uint32_t f_xo = L.flags + kFXo;
     const int NB = (Cp + 65 + kBlk - 1) / kBlk;  // lane 63 reaches step Cp+64 (element of column Cp)
+    // The block loop's bound.  A wait that fails (its watchdog, or another wave's error) sets the error
+    // word and this bound to 0: the loop test, which reads the bound anyway, ends the strip, and no
+    // block carries an exit of its own.  A block already under way (the second of a pair) runs to its
+    // end on whatever the rings hold, without waiting again -- every address it forms is masked into
+    // its ring or bounded by the pair's geometry -- and the launch fails on the error word.
+    int nbEnd = NB;
     // header-column slots of this lane's rows: tile row iT, elements ea .. ea+K-1 (one tile)
     const int iT = (rl - 1) / tBy;
     const int ea = rl - iT * tBy;
@@ -265,6 +272,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
 #define GSA_LDG_T() ldgT()
 #endif
     auto spin = [&](int b) {
+        if (nbEnd == 0) return false;  // a wait failed before: the strip is leaving
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         const uint64_t c0 = (kLedger && a.stamps) ? __builtin_amdgcn_s_memtime() : 0;
         for (int it = 1;; ++it)
@@ -283,6 +291,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
             if (__builtin_amdgcn_s_memrealtime() - t0 > a.spin || ((it & 31) == 0 && err_set(a)))
             {
                 atomicOr(a.err, 1u);
+                nbEnd = 0;
                 return false;
             }
         }
@@ -494,7 +503,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
             // the compiler resolves with lgkmcnt(1) there -- a wait for the whole LDS queue (the
             // profile reads and the hand-off writes) on the critical path of every block
             asm volatile("" ::"v"(rpin), "v"(rpco), "v"(rpxo), "v"(rsink));
-            if (slack < kBlk * b + 64 + kBlk && !spin(b)) return false;
+            if (slack < kBlk * b + 64 + kBlk) spin(b);  // (a failed wait: nbEnd)
         }
         if (PT == 3 && b > 0)
             halo_stage(b);
@@ -579,13 +588,14 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
                 flag_st(xsWords + 4u * (uint32_t)(2 * NS + w), max(0, kBlk * (b + 1) - 2 * tBx - 64));
                 // room in the staging ring for the next 16 blocks (the storer keeps up: rarely waits)
                 const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-                for (unsigned it = 1; flag_ld(xsWords + 4u * (uint32_t)(NS + w)) + kXD < b + 1 + 16; ++it)
+                for (unsigned it = 1; nbEnd != 0 && flag_ld(xsWords + 4u * (uint32_t)(NS + w)) + kXD < b + 1 + 16; ++it)
                 {
                     __builtin_amdgcn_s_sleep(1);
                     if (__builtin_amdgcn_s_memrealtime() - t0 > a.spin || ((it & 31) == 0 && err_set(a)))
                     {
                         atomicOr(a.err, 1u);
-                        return false;
+                        nbEnd = 0;  // (leaves like a failed spin())
+                        break;
                     }
                 }
             }
@@ -640,6 +650,7 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
             {
                 nbb += tBx / kBlk;
                 ++jb;
+                if (jb >= tcols) nbb = kNoCap;  // (advance())
                 hcolP += (size_t)(tBy + 1);
                 if (pt && (jb % a.ptChunk == 0 || jb == tcols)) ptPend = jb;
             }
@@ -650,29 +661,38 @@ __device__ __forceinline__ void kr_strip(const StripArgs& a, const KrLds& L, int
         ldg[1] += lt2 - lt1;
         ldg[2] += ldgEnd - lt2;
 #endif
-        return true;
     };
 
     // the block captures a header column iff it is one of the 4 blocks from the next boundary's
     // (uniform; tBx >= 64 keeps the boundaries 4 blocks apart)
     // (a two-tile-row ticket's second half past the last tile row computes padding only)
     const bool capRows = 64 * K * NS <= kSparseTileBy || (r0 - 1) / tBy < a.trows;
-    auto advance = [&](int b) { return b >= nbb && jb < tcols && capRows; };
     using T = std::integral_constant<bool, true>;
     using F = std::integral_constant<bool, false>;
     constexpr int kRampBlocks = 64 / kBlk;  // columns <= 0 occur only in the first 64 steps
     int b = 0;
+    // a strip with no (more) header column to capture has its next boundary at kNoCap, so the test
+    // per block is one compare
+    if (!(capRows && jb < tcols)) nbb = kNoCap;
+    auto advance = [&](int b) { return b >= nbb; };
+    // The ramp's 4 blocks, then whole pairs of blocks (the profile registers qA / qB alternate) in a
+    // straight-line body with ONE loop test, then the odd block if NB is odd (NB >= 5).  No block has
+    // an exit: a failed wait ends the loop through nbEnd (above).  The exits of a block() returning
+    // bool were ~14 scalar instructions per block outside the steps (100k 4.96 -> 4.80 ms,
+    // profiles/r09_strip_loop_ab.txt; scalar work taken out of the steps themselves only leaves
+    // s_nop in their DPP hazard slots and gains nothing, same file).
     for (; b < kRampBlocks; b += 2)
     {
-        if (!block(b, qA, qB, T(), false)) return;
-        if (!block(b + 1, qB, qA, T(), false)) return;
+        block(b, qA, qB, T(), false);
+        block(b + 1, qB, qA, T(), false);
     }
-    for (; b < NB; b += 2)
+    for (; b + 1 < nbEnd; b += 2)
     {
-        if (!block(b, qA, qB, F(), advance(b))) return;
-        if (b + 1 >= NB) break;
-        if (!block(b + 1, qB, qA, F(), advance(b + 1))) return;
+        block(b, qA, qB, F(), advance(b));
+        block(b + 1, qB, qA, F(), advance(b + 1));
     }
+    if (b < nbEnd) block(b, qA, qB, F(), advance(b));
+    if (nbEnd == 0) return;
     if (kLedger && a.stamps && lane == 0)
     {
         a.stamps[kLedgerWords * w + 4] = spinCyc;
