@@ -164,6 +164,22 @@ class AlignPairBandInfo(ctypes.Structure):
                 ("score_ms", ctypes.c_float), ("walk_ms", ctypes.c_float)]
 
 
+class AlignBatchBandPair(ctypes.Structure):
+    """gsa_align_batch_band_pair (include/gsa.h): one pair of the last gsa_align_batch_band_dev call."""
+    _fields_ = [("band_lo", ctypes.c_int64), ("band_hi", ctypes.c_int64), ("code_bytes", ctypes.c_int64),
+                ("strips", ctypes.c_int32), ("supersteps", ctypes.c_int32), ("proved_optimal", ctypes.c_int32),
+                ("round", ctypes.c_int32)]
+
+
+class AlignBatchBandInfo(ctypes.Structure):
+    """gsa_align_batch_band_info (include/gsa.h): what the last gsa_align_batch_band_dev call ran."""
+    _fields_ = [("batch_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32), ("nocode_pairs", ctypes.c_int32),
+                ("rounds", ctypes.c_int32), ("waves", ctypes.c_int32), ("strip_rows", ctypes.c_int32),
+                ("code_bytes", ctypes.c_int64),
+                ("fill_ms", ctypes.c_float), ("nocode_ms", ctypes.c_float), ("walk_ms", ctypes.c_float),
+                ("pad0", ctypes.c_int32)]
+
+
 class AlignBatchInfo(ctypes.Structure):
     """gsa_align_batch_info (include/gsa.h): what the last gsa_align_batch_dev call ran."""
     _fields_ = [("batch_pairs", ctypes.c_int32), ("alone_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32),
@@ -295,6 +311,14 @@ SIGNATURES = {
     "gsa_align_pair_band_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _i64,
                                                ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                                ctypes.POINTER(AlignPairBandInfo), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_band_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32,
+                                                ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32, _i32,
+                                                ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_batch_band_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32,
+                                                ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32, _i32, _i64,
+                                                ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
+                                                ctypes.POINTER(AlignBatchBandPair), ctypes.POINTER(AlignBatchBandInfo),
+                                                ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
@@ -1276,6 +1300,119 @@ class Engine:
         element in front, as score_batch() takes them; sequences and table are uploaded through torch."""
         ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
         return self.align_batch_semi_dev(ptrs, dS, substsz, gapo, gape, 0, scratch_limit)
+
+    # -- long pairs, banded: scores and alignments of a batch in one call (DESIGN.md 2.2q) --
+
+    @staticmethod
+    def _band_arrays(n: int, bands):
+        if len(bands) != n:
+            raise ValueError("one (band_lo, band_hi) per pair")
+        lo, hi = (ctypes.c_int64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))()
+        for k, (a, b) in enumerate(bands):
+            lo[k], hi[k] = int(a), int(b)
+        return lo, hi
+
+    def score_band_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                             stream: Optional[int] = None, *, bands, waves: int = 0, max_workgroups: int = 0) -> list:
+        """Banded global scores of many device-resident pairs in one launch (gsa_score_band_batch_dev;
+        synchronous).  `pairs` as score_semi_batch_dev takes it, `bands` a sequence of (band_lo,
+        band_hi), one per pair.  One dict per pair, in order, equal to score_band_dev's for that pair
+        alone except "kernel_ms", which is the hipEvent time of the whole call's kernel in every dict.
+        `waves` is the waves per workgroup (4, 8, 16; 0: the smallest that serves every pair),
+        `max_workgroups` caps the grid (0: all resident); no result depends on either."""
+        n = len(pairs)
+        lo, hi = self._band_arrays(n, bands)
+        arr = (PairDev * max(n, 1))()
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+        res = (ScoreResult * max(n, 1))()
+        ms = ctypes.c_float(0.0)
+        st = lib().gsa_score_band_batch_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                            lo, hi, int(waves), int(max_workgroups), res, ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_band_batch_dev")
+        return [{"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end), "kernel_ms": float(ms.value)}
+                for r in res[:n]]
+
+    @staticmethod
+    def _bands_of(pairs, bands, band):
+        """The bands of the host batch forms: `bands` as given, or `band` through _band_of per pair;
+        exactly one of the two, else ValueError."""
+        if (bands is None) == (band is None):
+            raise ValueError("give either bands or band")
+        if bands is not None:
+            return [(int(a), int(b)) for a, b in bands]
+        return [Engine._band_of(len(y) - 1, len(x) - 1, None, None, band) for y, x in pairs]
+
+    def score_band_batch(self, pairs, subst, gapo: int, gape: Optional[int] = None, *, bands=None,
+                         band: Optional[int] = None, waves: int = 0, max_workgroups: int = 0) -> list:
+        """score_band_batch_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the header
+        element in front, as score_batch() takes them.  The bands as bands=[(band_lo, band_hi), ...] or
+        band=k, applied per pair as score_band() applies it; exactly one of the two forms, else
+        ValueError."""
+        bl = self._bands_of(pairs, bands, band)
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.score_band_batch_dev(ptrs, dS, substsz, gapo, gape, bands=bl, waves=waves,
+                                         max_workgroups=max_workgroups)
+
+    def align_batch_band_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                             max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None, *, bands,
+                             waves: int = 0) -> list:
+        """The banded global alignments of many device-resident long pairs, traced on the device
+        together (gsa_align_batch_band_dev; synchronous).  `pairs` and `bands` as score_band_batch_dev
+        takes them.  One dict per pair, in order, with align_pair_band_dev's keys and, "kernel_ms"
+        apart (the hipEvent time of the whole call's kernels in every dict), its values for that pair
+        alone; "status" 1: the pair's move codes exceed `scratch_limit`, or its values the coded
+        fill's range (score and end cell only).  `scratch_limit` is the bytes of move codes held at
+        once (0: the default, 8 GiB).  last_align_batch_band_info() says what ran, pair by pair."""
+        n = len(pairs)
+        lo, hi = self._band_arrays(n, bands)
+        arr = (PairDev * max(n, 1))()
+        cap = 0
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+            cap += 2 * (max(ar - 1, 0) + max(ac - 1, 0)) + 1  # 2 (R + C) + 1 bytes always suffice
+        res = (AlignDbResult * max(n, 1))()
+        pinfo = (AlignBatchBandPair * max(n, 1))()
+        info = AlignBatchBandInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        st = lib().gsa_align_batch_band_dev(self._h, n, arr, subst_ptr, substsz, gapo, gapo if gape is None else gape,
+                                            lo, hi, int(waves), int(max_workgroups), int(scratch_limit), res, buf, cap,
+                                            ctypes.byref(need), pinfo, ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_batch_band_dev")
+        d = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+             for k, t in info._fields_ if not k.startswith("pad")}
+        d["pairs"] = [{k: int(getattr(q, k)) for k, _ in q._fields_} for q in pinfo[:n]]
+        self._align_batch_band_info = d
+        raw = buf.raw
+        return [{"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start), "j_start": int(r.j_start),
+                 "i_end": int(r.i_end), "j_end": int(r.j_end),
+                 "cigar": raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else "",
+                 "kernel_ms": float(ms.value)} for r in res[:n]]
+
+    def last_align_batch_band_info(self) -> dict:
+        """gsa_align_batch_band_info of the last align_batch_band_dev call on this engine: "batch_pairs"
+        (traced on the device), "host_pairs", "nocode_pairs" (status 1), "rounds" (fill + walk launch
+        pairs), "waves" (per workgroup), "strip_rows", "code_bytes" (peak bytes of move codes held at
+        once), "fill_ms", "nocode_ms" and "walk_ms"; "pairs" is the list of the pairs' own values:
+        "band_lo" and "band_hi" (clamped), "code_bytes", "strips", "supersteps", "proved_optimal" and
+        "round" (-1: answered on the host, -2: ran without codes)."""
+        info = getattr(self, "_align_batch_band_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_batch_band_info: no align_batch_band_dev call yet")
+        d = dict(info)
+        d["pairs"] = [dict(q) for q in info["pairs"]]
+        return d
+
+    def align_batch_band(self, pairs, subst, gapo: int, gape: Optional[int] = None, scratch_limit: int = 0, *,
+                         bands=None, band: Optional[int] = None, waves: int = 0, max_workgroups: int = 0) -> list:
+        """align_batch_band_dev over host arrays, with the pairs and the bands as score_band_batch()
+        takes them."""
+        bl = self._bands_of(pairs, bands, band)
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.align_batch_band_dev(ptrs, dS, substsz, gapo, gape, max_workgroups, scratch_limit, bands=bl,
+                                         waves=waves)
 
     # -- long pairs, overlap (dovetail): scores and alignments of a batch in one call (DESIGN.md 2.2n) --
 

@@ -3,7 +3,7 @@
 // gsa_align_db_dev, gsa_align_db_multi_dev, gsa_align_pair_dev and gsa_align_batch_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
 // (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
 // nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip); the banded calls
-// gsa_score_band_dev and gsa_align_pair_band_dev on nw_band.hip.  The context
+// gsa_score_band_dev and gsa_align_pair_band_dev on nw_band.hip, their batch forms on nw_band_batch.hip.  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "../../include/gsa.h"
 #include "gsa_ctx.h"
 #include "nw_band.h"
+#include "nw_band_batch.h"
 #include "nw_bidi.h"
 #include "nw_krow.h"
 #include "nw_lanes.h"
@@ -4180,6 +4181,305 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
     return GSA_SUCCESS;
 }
 
+// gsa_score_band_batch_dev and gsa_align_batch_band_dev (align: the latter): every pair is
+// checked and planned as band_impl does (nothing is enqueued before all passed), the pairs with an empty
+// side are answered here, the others run on nw_band_batch.hip: one launch without codes for the pairs
+// that get none (all pairs of the score call), then the rounds of nw_band_batch_plan.h, each one upload,
+// one fill launch, one walk launch and one copy back.  Scratch: kBufPairBatchTab ([0] the claim counter,
+// [64] the round's descriptors, then its walk arguments), kBufPairBatchRec (the round's result words,
+// walk records and move bytes, copied back as one), kBufPairCodes.  gsa_last_launch's record is not
+// touched.
+int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                    int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
+                    int32_t max_workgroups, bool align, int64_t scratch_limit, gsa_score_result* sout, gsa_align_db_result* out,
+                    char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_batch_band_pair* pair_info,
+                    gsa_align_batch_band_info* info, float* kernel_ms, hipStream_t st)
+{
+    if (!ctx || npairs < 0 || !pairs || !subst || !band_lo || !band_hi || (align ? !out : !sout)) return GSA_ERROR_INVALID_VALUE;
+    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
+    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
+    if (max_workgroups < 0 || (waves != 0 && waves != 4 && waves != 8 && waves != 16)) return GSA_ERROR_INVALID_VALUE;
+    if (align && (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar))) return GSA_ERROR_INVALID_VALUE;
+    struct Bp
+    {
+        int64_t R, C;
+        gsa::BandPlan plan;  // (lo, hi: also of a pair with an empty side)
+        bool host, codes;
+    };
+    std::vector<Bp> bp((size_t)npairs);
+    bool anyDev = false;
+    for (int p = 0; p < npairs; ++p)
+    {
+        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
+        Bp& b = bp[(size_t)p];
+        b.R = pairs[p].adjrows - 1;
+        b.C = pairs[p].adjcols - 1;
+        if (b.R >= (1ll << 30) || b.C >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;  // the kernel's int32 cell indices
+        int64_t lo = band_lo[p], hi = band_hi[p];
+        if (!gsa::band_valid(b.R, b.C, lo, hi)) return GSA_ERROR_INVALID_VALUE;
+        gsa::band_clamp(b.R, b.C, &lo, &hi);
+        b.host = b.R == 0 || b.C == 0;
+        b.codes = false;
+        if (b.host)
+        {
+            b.plan.lo = lo;
+            b.plan.hi = hi;
+            bool stripOk = false;
+            if (b.R + b.C > 0 && score_ranges(b.R, b.C, 1, gapo, gape, 0, &stripOk) != GSA_SUCCESS) return GSA_ERROR_INVALID_VALUE;
+        }
+        else
+        {
+            if (!gsa::band_plan(b.R, b.C, lo, hi, &b.plan)) return GSA_ERROR_INVALID_VALUE;  // wider than the limit
+            if (waves != 0 && !gsa::band_waves_ok(waves, b.plan.strips, b.plan.nq)) return GSA_ERROR_INVALID_VALUE;
+            anyDev = true;
+        }
+    }
+    const int64_t limit = scratch_limit > 0 ? scratch_limit : gsa::kBandBatchScratch;
+    hipError_t e = hipSuccess;
+    long long pmax = 0;
+    if (anyDev)
+    {
+        if ((e = hipSetDevice(ctx->device)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
+        if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        const long long smax = subst_absmax(sub.data(), substsz);
+        pmax = std::max<long long>(0, *std::max_element(sub.begin(), sub.end()));
+        for (Bp& b : bp)
+        {
+            if (b.host) continue;
+            bool stripOk = false;
+            const int s = score_ranges(b.R, b.C, smax, gapo, gape, 0, &stripOk);
+            if (s != GSA_SUCCESS) return s;
+            // the fill with codes keeps 4 x value + source: |H| <= B (score_ranges' bound, which holds in the band)
+            const bool valOk =
+                smax * std::min(b.R, b.C) + (long long)(-gapo) + (b.R + b.C) * (long long)(-gape) < gsa::kDbTraceMaxValue;
+            b.codes = align && valOk && b.plan.codeBytes <= limit;
+        }
+    }
+    // every pair passed: from here on the call answers
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (cigar_need) *cigar_need = 0;
+    gsa_align_batch_band_info inf;
+    std::memset(&inf, 0, sizeof(inf));
+    std::vector<gsa_align_db_result> res((size_t)npairs);
+    if (npairs > 0) std::memset(res.data(), 0, res.size() * sizeof(gsa_align_db_result));
+    std::vector<std::string> cig((size_t)npairs);
+    std::vector<int> roundOf((size_t)npairs, -1);
+    std::vector<int64_t> codeBytes((size_t)npairs, -1);
+    std::vector<int> nocode;
+    for (int p = 0; p < npairs; ++p)
+    {
+        const Bp& b = bp[(size_t)p];
+        gsa_align_db_result& r = res[(size_t)p];
+        r.i_end = b.R;
+        r.j_end = b.C;
+        if (b.host)
+        {
+            // one boundary, answered on the host as band_impl does: row 0 is E only, column 0 F only
+            const int64_t k = b.R + b.C;
+            if (k > 0)
+            {
+                r.score = (int32_t)(gapo + (k - 1) * gape);
+                cig[(size_t)p] = std::to_string(k) + (b.R > 0 ? 'I' : 'D');
+            }
+            inf.host_pairs += 1;
+        }
+        else if (b.codes)
+            codeBytes[(size_t)p] = b.plan.codeBytes;
+        else
+        {
+            nocode.push_back(p);
+            roundOf[(size_t)p] = -2;
+            r.status = 1;
+        }
+    }
+    const gsa::BandBatchRounds rounds = gsa::band_batch_rounds(codeBytes, limit);
+    if (!rounds.nocode.empty()) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (b.codes holds the limit)
+    inf.nocode_pairs = align ? (int32_t)nocode.size() : 0;
+    inf.rounds = (int32_t)rounds.rounds.size();
+    inf.code_bytes = rounds.peakBytes;
+    if (anyDev)
+    {
+        inf.strip_rows = gsa::kBandTR;
+        for (hipEvent_t& ev : ctx->adbev)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    }
+    // launch 0: the pairs without codes; then the rounds
+    std::vector<char> blob, back;
+    for (size_t l = 0; l < 1 + rounds.rounds.size(); ++l)
+    {
+        const bool codes = l > 0;
+        const std::vector<int>& members = codes ? rounds.rounds[l - 1] : nocode;
+        if (members.empty()) continue;
+        const size_t n = members.size();
+        // the order the workgroups claim the pairs in, and the waves all of them can run on
+        std::vector<int64_t> T(n), strips(n), nq(n);
+        for (size_t k = 0; k < n; ++k)
+        {
+            const gsa::BandPlan& pl = bp[(size_t)members[k]].plan;
+            T[k] = pl.T;
+            strips[k] = pl.strips;
+            nq[k] = pl.nq;
+        }
+        const std::vector<int> order = gsa::band_batch_order(T);
+        const int nwv = gsa::band_batch_pick_waves(waves, strips.data(), nq.data(), n);
+        if (nwv == 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (checked per pair above)
+        inf.waves = std::max(inf.waves, nwv);
+        // the device tables: [counter | descriptors | walk arguments] and [result words | records | moves]
+        const size_t descOff = 64, walkOff = descOff + ((n * sizeof(gsa::BandDesc) + 63) & ~(size_t)63);
+        const size_t tabBytes = walkOff + (codes ? n * sizeof(gsa::BandWalkArgs) : 0);
+        const size_t recOff = (n * 8 + 63) & ~(size_t)63, movOff = recOff + (codes ? n * sizeof(gsa::BandWalkRec) : 0);
+        std::vector<int64_t> mvAt(n, 0), cdAt(n, 0);
+        int64_t movTotal = 0, codeTotal = 0;
+        if (codes)
+            for (size_t k = 0; k < n; ++k)
+            {
+                const Bp& b = bp[(size_t)members[(size_t)order[k]]];
+                mvAt[k] = movTotal;
+                cdAt[k] = codeTotal;
+                movTotal += b.R + b.C;
+                codeTotal += b.plan.codeBytes;
+            }
+        int s;
+        if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS ||
+            (s = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], movOff + (size_t)movTotal, 4096)) != GSA_SUCCESS ||
+            (codes && (s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)codeTotal, 4096)) != GSA_SUCCESS))
+            return s;
+        char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
+        char* const drec = ctx->buf[kBufPairBatchRec].as<char>();
+        unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
+        blob.assign(tabBytes, 0);
+        for (size_t k = 0; k < n; ++k)
+        {
+            const int p = members[(size_t)order[k]];
+            const Bp& b = bp[(size_t)p];
+            gsa::BandDesc d;
+            std::memset(&d, 0, sizeof(d));
+            d.seqY = pairs[p].seqY;
+            d.seqX = pairs[p].seqX;
+            d.codes = codes ? dcodes + cdAt[k] : nullptr;
+            d.result = (int*)drec + 2 * k;
+            d.stripBytes = b.plan.stripBytes;
+            d.R = (int)b.R;
+            d.C = (int)b.C;
+            d.lo = (int)b.plan.lo;
+            d.hi = (int)b.plan.hi;
+            d.strips = (int)b.plan.strips;
+            d.nq = (int)b.plan.nq;
+            d.T = (int)b.plan.T;
+            d.Wc = (int)b.plan.Wc;
+            std::memcpy(blob.data() + descOff + k * sizeof(d), &d, sizeof(d));
+            if (!codes) continue;
+            gsa::BandWalkArgs w;
+            std::memset(&w, 0, sizeof(w));
+            w.seqY = d.seqY;
+            w.seqX = d.seqX;
+            w.codes = d.codes;
+            w.stripBytes = d.stripBytes;
+            w.R = d.R;
+            w.C = d.C;
+            w.lo = d.lo;
+            w.hi = d.hi;
+            w.rec = (gsa::BandWalkRec*)(drec + recOff) + k;
+            w.moves = (unsigned char*)drec + movOff + mvAt[k];
+            std::memcpy(blob.data() + walkOff + k * sizeof(w), &w, sizeof(w));
+        }
+        int grid = 0, walkGrid = (int)std::min<size_t>(n, 65535);
+        if (max_workgroups > 0) walkGrid = std::min(walkGrid, (int)max_workgroups);
+        if ((e = gsa::band_batch_fill_grid(gapo != gape, codes, nwv, (int)n, max_workgroups, &grid)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        // the result words and the walks' records start from zero: a kernel that wrote nothing is seen
+        if ((e = hipMemsetAsync(drec, 0, movOff, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        if ((e = gsa::launch_band_batch((const gsa::BandDesc*)(dtab + descOff), (int)n, (unsigned*)dtab, nwv, grid, subst, substsz,
+                                        gapo, gape, codes, codes ? (const gsa::BandWalkArgs*)(dtab + walkOff) : nullptr, walkGrid,
+                                        ctx->adbev, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        back.resize(movOff + (size_t)movTotal);
+        if ((e = hipMemcpyAsync(back.data(), drec, back.size(), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        float fill = 0.f, walk = 0.f;
+        (void)hipEventElapsedTime(&fill, ctx->adbev[0], ctx->adbev[1]);
+        if (codes) (void)hipEventElapsedTime(&walk, ctx->adbev[1], ctx->adbev[2]);
+        (codes ? inf.fill_ms : inf.nocode_ms) += fill;
+        inf.walk_ms += walk;
+        const int* const words = (const int*)back.data();
+        for (size_t k = 0; k < n; ++k)
+        {
+            const int p = members[(size_t)order[k]];
+            const Bp& b = bp[(size_t)p];
+            if (words[2 * k + 1] != 1) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            res[(size_t)p].score = words[2 * k];
+            if (!codes) continue;
+            roundOf[(size_t)p] = (int)l - 1;
+            gsa::BandWalkRec rec;
+            std::memcpy(&rec, back.data() + recOff + k * sizeof(rec), sizeof(rec));
+            // a step off the band, a record out of range, or a walk that did not end at (0, 0)
+            if (rec.offband || !rec.done || rec.n < 0 || rec.n > b.R + b.C || rec.i != 0 || rec.j != 0)
+                return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            cig[(size_t)p] = fold_cigar((const unsigned char*)back.data() + movOff + mvAt[k], rec.n);
+        }
+        if (codes) inf.batch_pairs += (int32_t)n;
+    }
+    if (!align)
+    {
+        for (int p = 0; p < npairs; ++p)
+        {
+            sout[p].score = res[(size_t)p].score;
+            sout[p].i_end = bp[(size_t)p].R;
+            sout[p].j_end = bp[(size_t)p].C;
+            sout[p].calc_kernel_ms = 0.f;
+        }
+        if (kernel_ms) *kernel_ms = inf.nocode_ms;
+        return GSA_SUCCESS;
+    }
+    int64_t at = 0;
+    for (int p = 0; p < npairs; ++p)
+    {
+        gsa_align_db_result& r = res[(size_t)p];
+        const Bp& b = bp[(size_t)p];
+        const int64_t len = (int64_t)cig[(size_t)p].size();
+        if (r.status == 0)
+        {
+            if (at + len + 1 <= cigar_cap)
+            {
+                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
+                r.cigar_off = at;
+                r.cigar_len = len;
+            }
+            else
+                r.status = 2;
+            at += len + 1;
+        }
+        out[p] = r;
+        if (pair_info)
+        {
+            gsa_align_batch_band_pair& pi = pair_info[p];
+            std::memset(&pi, 0, sizeof(pi));
+            pi.band_lo = b.plan.lo;
+            pi.band_hi = b.plan.hi;
+            pi.round = roundOf[(size_t)p];
+            pi.proved_optimal = 1;
+            if (!b.host)
+            {
+                pi.code_bytes = b.plan.codeBytes;
+                pi.strips = (int32_t)b.plan.strips;
+                pi.supersteps = (int32_t)b.plan.T;
+                pi.proved_optimal = gsa::band_certificate(b.R, b.C, b.plan.lo, b.plan.hi, pmax, gapo, gape, r.score);
+            }
+        }
+    }
+    if (cigar_need) *cigar_need = at;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.nocode_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4203,6 +4503,27 @@ int gsa_align_pair_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
     return band_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, true, scratch_limit,
                      nullptr, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_band_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                             int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
+                             int32_t max_workgroups, gsa_score_result* out, float* batch_kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, false, 0, out,
+                           nullptr, nullptr, 0, nullptr, nullptr, nullptr, batch_kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_batch_band_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                             int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
+                             int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                             int64_t cigar_cap, int64_t* cigar_need, gsa_align_batch_band_pair* pair_info,
+                             gsa_align_batch_band_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, true,
+                           scratch_limit, nullptr, out, cigar, cigar_cap, cigar_need, pair_info, info, kernel_ms,
+                           pick_stream(ctx, stream));
 }
 
 int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,

@@ -1275,6 +1275,92 @@ int gsa_align_pair_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
                             int64_t cigar_cap, int64_t* cigar_need, gsa_align_pair_band_info* info, float* kernel_ms,
                             void* stream);
 
+/* Long pairs, banded: scores and alignments of a batch in one call.
+ *
+ * gsa_score_band_batch_dev: pairs is a HOST array (only seqY, adjrows, seqX and adjcols are read; two
+ * entries may name the same buffers), band_lo and band_hi host arrays with pair p's band at [p], out a
+ * host array of npairs results.  Synchronous.
+ * Semantics: out[p] is exactly what gsa_score_band_dev returns for pair p alone with band_lo[p],
+ * band_hi[p], with calc_kernel_ms 0, whatever the pair's position or neighbours in the list, the waves
+ * per workgroup and max_workgroups; *batch_kernel_ms (may be null) gets the hipEvent time of the
+ * launch.  Pairs with R = 0 or C = 0 are answered on the host as there.
+ * How (nw_band_batch.hip): one launch of the fill without move codes on a persistent grid of
+ * min(pairs, resident workgroups, max_workgroups) workgroups (max_workgroups 0: no cap).  A workgroup
+ * claims the next pair from one counter and runs gsa_score_band_dev's lockstep super-steps for it, the
+ * same device code, then claims again; the pairs are handed out by super-steps T descending, ties by
+ * index, so the longest start first.  Nothing polls memory and no workgroup waits for another.
+ * waves is the waves per workgroup: 4, 8 or 16, or 0 for the smallest of the three on which every pair
+ * of the launch with more strips than waves finds its wave free again, nq <= 6 waves with nq =
+ * ceil((W + TR + 62) / 64), that is W <= 1218 at 4 waves, 2754 at 8 and 5826 at 16.  It is an argument
+ * and no knob: no result depends on it.
+ * errorInvalidValue, before anything is enqueued and with out left as it was: npairs < 0, a null array,
+ * any one pair that gsa_score_band_dev refuses (an invalid band, a width over gsa_band_max_width(), the
+ * value range), a negative max_workgroups, a waves that is none of 0, 4, 8, 16 or that is too small
+ * for one of the pairs (more strips than waves and nq > 6 waves).  npairs = 0 succeeds with nothing
+ * launched.  The call adds no launch kind and no knob, leaves the record of gsa_last_launch and the
+ * fills' sticky error word alone, and counts its scratch in gsa_mem_stats. */
+int gsa_score_band_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                             int32_t substsz, int32_t gapo, int32_t gape, const int64_t* band_lo,
+                             const int64_t* band_hi, int32_t waves, int32_t max_workgroups, gsa_score_result* out,
+                             float* batch_kernel_ms, void* stream);
+
+typedef struct gsa_align_batch_band_pair {  /* one pair of the batch: gsa_align_pair_band_info's values */
+    int64_t band_lo, band_hi; /* the clamped band */
+    int64_t code_bytes;       /* bytes of move codes of the pair's band (also when it got none) */
+    int32_t strips;           /* strips that hold the rows 1 ... R (0: answered on the host) */
+    int32_t supersteps;       /* T of the pair */
+    int32_t proved_optimal;   /* the certificate of gsa_align_pair_band_dev */
+    int32_t round;            /* >= 0: the fill + walk round the pair ran in; -1: answered on the host;
+                                 -2: it ran without codes (status 1) */
+} gsa_align_batch_band_pair;
+
+typedef struct gsa_align_batch_band_info {  /* what the call ran; optional out-parameter */
+    int32_t batch_pairs;   /* pairs traced on the device */
+    int32_t host_pairs;    /* pairs answered on the host: an empty side */
+    int32_t nocode_pairs;  /* pairs that ran without codes: status 1 */
+    int32_t rounds;        /* fill + walk launch pairs */
+    int32_t waves;         /* waves per workgroup the launches used (the largest, when they differ) */
+    int32_t strip_rows;    /* TR: rows of a strip (256); 0: nothing was launched */
+    int64_t code_bytes;    /* peak bytes of move codes held at once */
+    float fill_ms, nocode_ms, walk_ms; /* hipEvent time of the fills with codes, of the launch without and of
+                                          the walks, summed over the rounds */
+    int32_t pad0;
+} gsa_align_batch_band_info;
+
+/* The banded alignments of npairs pairs traced on the device together: gsa_score_band_batch_dev's
+ * arguments, gsa_align_batch_dev's result array and CIGAR buffer.  Synchronous.
+ * Semantics: out[p] is, field for field, what gsa_align_pair_band_dev returns for pair p alone with
+ * band_lo[p], band_hi[p] -- score, both cells, status and the CIGAR -- whatever the pair's position or
+ * neighbours in the list, the waves per workgroup, max_workgroups, the round it lands in, or whether two
+ * entries name the same buffers.  pair_info[p] (a host array of npairs entries, may be null) holds the
+ * single call's info values of pair p and its round.  The CIGAR buffer follows gsa_align_batch_dev's
+ * rules: the strings back to back in pair order, NUL-terminated, a pair's offset independent of
+ * cigar_cap, status 2 for a string that does not fit, *cigar_need (may be null) the bytes all need.
+ * How: a pair's move codes are held whole, strips x (W + TR - 1) x TR / 2 bytes.  scratch_limit is the
+ * bytes of codes the call may hold at once; 0 is the default, 8 GiB.  The pairs that get codes are taken
+ * by code bytes descending, ties by index; a round takes every pair that still fits the bytes left,
+ * first fit in that order, and is one upload of its descriptors, one fill launch on the persistent grid
+ * above with the 4-bit codes written in the same pass, one walk launch -- one wave per pair, lane 0
+ * walking as in the single call, workgroups taking the pairs b, b + grid, ... under max_workgroups --
+ * and one copy that brings all records and move bytes of the round back.  A launch takes its waves
+ * from its widest pair.
+ * Status 1 -- score and end cell from the fill without codes, start cell 0, an empty CIGAR -- for a pair
+ * whose own code_bytes exceed scratch_limit or whose value bound B reaches 2^26: the single call's
+ * rule, with the batch's limit.  These pairs run in one launch without codes before the rounds; the
+ * other pairs are unaffected.
+ * errorInvalidValue, before anything is enqueued and with out left as it was: everything
+ * gsa_score_band_batch_dev refuses, a negative scratch_limit or cigar_cap, a null cigar with
+ * cigar_cap > 0.  A walk record that comes back out of range, or a step off the band, is
+ * errorKernelFailure.  *info (may be null) says what the call ran; *kernel_ms (may be null) gets the
+ * hipEvent time of all kernels of the call.  All scratch is counted in gsa_mem_stats; the record of
+ * gsa_last_launch and the fills' sticky error word are left alone. */
+int gsa_align_batch_band_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                             int32_t substsz, int32_t gapo, int32_t gape, const int64_t* band_lo,
+                             const int64_t* band_hi, int32_t waves, int32_t max_workgroups, int64_t scratch_limit,
+                             gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                             gsa_align_batch_band_pair* pair_info, gsa_align_batch_band_info* info, float* kernel_ms,
+                             void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
