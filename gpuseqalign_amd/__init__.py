@@ -180,6 +180,24 @@ class AlignBatchBandInfo(ctypes.Structure):
                 ("pad0", ctypes.c_int32)]
 
 
+class AlignPairBandExtInfo(ctypes.Structure):
+    """gsa_align_pair_band_ext_info (include/gsa.h): what the last gsa_align_pair_band_ext_dev call ran."""
+    _fields_ = AlignPairBandInfo._fields_ + [("rows_used", ctypes.c_int64), ("cols_used", ctypes.c_int64)]
+
+
+class AlignBatchBandExtPair(ctypes.Structure):
+    """gsa_align_batch_band_ext_pair (include/gsa.h): one pair of the last gsa_align_batch_band_ext_dev call."""
+    _fields_ = [("band_lo", ctypes.c_int64), ("band_hi", ctypes.c_int64), ("code_bytes", ctypes.c_int64),
+                ("rows_used", ctypes.c_int64), ("cols_used", ctypes.c_int64),
+                ("strips", ctypes.c_int32), ("supersteps", ctypes.c_int32), ("proved_optimal", ctypes.c_int32),
+                ("round", ctypes.c_int32)]
+
+
+class AlignBatchBandExtInfo(ctypes.Structure):
+    """gsa_align_batch_band_ext_info (include/gsa.h): what the last gsa_align_batch_band_ext_dev call ran."""
+    _fields_ = AlignBatchBandInfo._fields_ + [("rows_used", ctypes.c_int64), ("cols_used", ctypes.c_int64)]
+
+
 class AlignBatchInfo(ctypes.Structure):
     """gsa_align_batch_info (include/gsa.h): what the last gsa_align_batch_dev call ran."""
     _fields_ = [("batch_pairs", ctypes.c_int32), ("alone_pairs", ctypes.c_int32), ("host_pairs", ctypes.c_int32),
@@ -319,6 +337,21 @@ SIGNATURES = {
                                                 ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64, ctypes.POINTER(_i64),
                                                 ctypes.POINTER(AlignBatchBandPair), ctypes.POINTER(AlignBatchBandInfo),
                                                 ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_band_ext_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64,
+                                              ctypes.POINTER(ScoreResult), _vp]),
+    "gsa_align_pair_band_ext_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i64, _i64, _i64,
+                                                   ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                                   ctypes.POINTER(_i64), ctypes.POINTER(AlignPairBandExtInfo),
+                                                   ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_score_band_ext_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32,
+                                                    ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32, _i32,
+                                                    ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
+    "gsa_align_batch_band_ext_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32,
+                                                    ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32, _i32, _i64,
+                                                    ctypes.POINTER(AlignDbResult), ctypes.c_char_p, _i64,
+                                                    ctypes.POINTER(_i64), ctypes.POINTER(AlignBatchBandExtPair),
+                                                    ctypes.POINTER(AlignBatchBandExtInfo),
+                                                    ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_batch_dev": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(PairDev), _vp, _i32, _i32, _i32, _i32,
                                            ctypes.POINTER(ScoreResult), ctypes.POINTER(ctypes.c_float), _vp]),
     "gsa_score_db_dev": (ctypes.c_int, [_vp, _vp, _i32, _vp, ctypes.POINTER(_i64), _i32, _vp, _i32, _i32, _i32, _i32,
@@ -940,6 +973,92 @@ class Engine:
         return self.align_pair_band_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
                                         gapo, gape, lo, hi, scratch_limit)
 
+    # -- long pairs, banded extension: from (0, 0) to the best cell of the band --
+    def score_band_ext_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int, substsz: int,
+                           gapo: int, gape: Optional[int], band_lo: int, band_hi: int, stream: Optional[int] = None) -> dict:
+        """Banded extension score of one device-resident pair (gsa_score_band_ext_dev; synchronous):
+        score_band_dev's arguments; the score is the largest H of the band, never negative, and the
+        end cell the first maximal one in row-major order.  The band must hold (0, 0) -- not (R, C) --
+        and, clamped to the matrix, at most band_max_width() diagonals."""
+        r = ScoreResult()
+        st = lib().gsa_score_band_ext_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                          gapo if gape is None else gape, int(band_lo), int(band_hi), ctypes.byref(r),
+                                          stream)
+        self._check(st, "gsa_score_band_ext_dev")
+        return {"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end),
+                "kernel_ms": float(r.calc_kernel_ms)}
+
+    @staticmethod
+    def _band_ext_of(band_lo, band_hi, band):
+        """The band of the extension's host forms: (band_lo, band_hi) as given, or band=w for (-w, w).
+        Exactly one of the two forms."""
+        pair = band_lo is not None or band_hi is not None
+        if pair == (band is not None) or (pair and (band_lo is None or band_hi is None)):
+            raise ValueError("give either band_lo and band_hi, or band")
+        return (int(band_lo), int(band_hi)) if pair else (-int(band), int(band))
+
+    def _upload_pair(self, seqY, seqX, subst):
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(_c32(a)).to(dev)
+        subst = _c32(subst)
+        dS, dY, dX = up(subst.ravel()), up(seqY), up(seqX)
+        torch.cuda.synchronize(dev)
+        return dS, dY, dX, int(round(np.sqrt(subst.size)))
+
+    def score_band_ext(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None, band_lo: Optional[int] = None,
+                       band_hi: Optional[int] = None, band: Optional[int] = None) -> dict:
+        """score_band_ext_dev over host arrays, the sequences with the header element in front.  The
+        band as (band_lo, band_hi), or band=w for (-w, w); exactly one of the two forms, else
+        ValueError."""
+        lo, hi = self._band_ext_of(band_lo, band_hi, band)
+        dS, dY, dX, substsz = self._upload_pair(seqY, seqX, subst)
+        return self.score_band_ext_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(), substsz,
+                                       gapo, gape, lo, hi)
+
+    def align_pair_band_ext_dev(self, seqY_ptr: int, adjrows: int, seqX_ptr: int, adjcols: int, subst_ptr: int,
+                                substsz: int, gapo: int, gape: Optional[int], band_lo: int, band_hi: int,
+                                scratch_limit: int = 0, stream: Optional[int] = None) -> dict:
+        """The banded extension alignment of one device-resident pair (gsa_align_pair_band_ext_dev;
+        synchronous): align_pair_band_dev's arguments and keys, from (0, 0) to the band's best cell;
+        status 1: score and end cell only.  last_align_pair_band_ext_info() says what ran."""
+        res = AlignDbResult()
+        info = AlignPairBandExtInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        # 2 (R + C) + 1 bytes always suffice
+        cap = 2 * (max(adjrows - 1, 0) + max(adjcols - 1, 0)) + 1
+        buf = ctypes.create_string_buffer(cap)
+        st = lib().gsa_align_pair_band_ext_dev(self._h, seqY_ptr, adjrows, seqX_ptr, adjcols, subst_ptr, substsz, gapo,
+                                               gapo if gape is None else gape, int(band_lo), int(band_hi),
+                                               int(scratch_limit), ctypes.byref(res), buf, cap, ctypes.byref(need),
+                                               ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_pair_band_ext_dev")
+        self._align_pair_band_ext_info = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+                                          for k, t in info._fields_ if k != "pad0"}
+        cig = buf.raw[res.cigar_off:res.cigar_off + res.cigar_len].decode() if res.status == 0 else ""
+        return {"score": int(res.score), "status": int(res.status), "i_start": int(res.i_start),
+                "j_start": int(res.j_start), "i_end": int(res.i_end), "j_end": int(res.j_end), "cigar": cig,
+                "kernel_ms": float(ms.value)}
+
+    def last_align_pair_band_ext_info(self) -> dict:
+        """gsa_align_pair_band_ext_info of the last align_pair_band_ext_dev call on this engine:
+        last_align_pair_band_info()'s keys, of the part of the pair the band reaches, and that part's
+        "rows_used" and "cols_used"; "proved_optimal" 1: the result is the unbanded extension's."""
+        info = getattr(self, "_align_pair_band_ext_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_pair_band_ext_info: no align_pair_band_ext_dev call yet")
+        return dict(info)
+
+    def align_pair_band_ext(self, seqY, seqX, subst, gapo: int, gape: Optional[int] = None,
+                            band_lo: Optional[int] = None, band_hi: Optional[int] = None, band: Optional[int] = None,
+                            scratch_limit: int = 0) -> dict:
+        """align_pair_band_ext_dev over host arrays, with the band as score_band_ext() takes it."""
+        lo, hi = self._band_ext_of(band_lo, band_hi, band)
+        dS, dY, dX, substsz = self._upload_pair(seqY, seqX, subst)
+        return self.align_pair_band_ext_dev(dY.data_ptr(), dY.numel(), dX.data_ptr(), dX.numel(), dS.data_ptr(),
+                                            substsz, gapo, gape, lo, hi, scratch_limit)
+
     def score_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
                         local: bool = False, stream: Optional[int] = None) -> list:
         """Score-only alignment of many device-resident pairs in one persistent launch
@@ -1413,6 +1532,103 @@ class Engine:
         ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
         return self.align_batch_band_dev(ptrs, dS, substsz, gapo, gape, max_workgroups, scratch_limit, bands=bl,
                                          waves=waves)
+
+    # -- long pairs, banded extension: scores and alignments of a batch in one call --
+
+    def score_band_ext_batch_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                                 stream: Optional[int] = None, *, bands, waves: int = 0, max_workgroups: int = 0) -> list:
+        """Banded extension scores of many device-resident pairs in one launch
+        (gsa_score_band_ext_batch_dev; synchronous): score_band_batch_dev's arguments.  One dict per
+        pair, in order, equal to score_band_ext_dev's for that pair alone except "kernel_ms", the
+        hipEvent time of the whole call's kernel in every dict."""
+        n = len(pairs)
+        lo, hi = self._band_arrays(n, bands)
+        arr = (PairDev * max(n, 1))()
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+        res = (ScoreResult * max(n, 1))()
+        ms = ctypes.c_float(0.0)
+        st = lib().gsa_score_band_ext_batch_dev(self._h, n, arr, subst_ptr, substsz, gapo,
+                                                gapo if gape is None else gape, lo, hi, int(waves), int(max_workgroups),
+                                                res, ctypes.byref(ms), stream)
+        self._check(st, "gsa_score_band_ext_batch_dev")
+        return [{"score": int(r.score), "i_end": int(r.i_end), "j_end": int(r.j_end), "kernel_ms": float(ms.value)}
+                for r in res[:n]]
+
+    @staticmethod
+    def _bands_ext_of(pairs, bands, band):
+        """The bands of the extension's host batch forms: `bands` as given, or band=w for (-w, w) per
+        pair; exactly one of the two, else ValueError."""
+        if (bands is None) == (band is None):
+            raise ValueError("give either bands or band")
+        if bands is not None:
+            return [(int(a), int(b)) for a, b in bands]
+        return [(-int(band), int(band)) for _ in pairs]
+
+    def score_band_ext_batch(self, pairs, subst, gapo: int, gape: Optional[int] = None, *, bands=None,
+                             band: Optional[int] = None, waves: int = 0, max_workgroups: int = 0) -> list:
+        """score_band_ext_batch_dev over host arrays: `pairs` is a sequence of (seqY, seqX) with the
+        header element in front.  The bands as bands=[(band_lo, band_hi), ...] or band=w for (-w, w)
+        on every pair; exactly one of the two forms, else ValueError."""
+        bl = self._bands_ext_of(pairs, bands, band)
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.score_band_ext_batch_dev(ptrs, dS, substsz, gapo, gape, bands=bl, waves=waves,
+                                             max_workgroups=max_workgroups)
+
+    def align_batch_band_ext_dev(self, pairs, subst_ptr: int, substsz: int, gapo: int, gape: Optional[int] = None,
+                                 max_workgroups: int = 0, scratch_limit: int = 0, stream: Optional[int] = None, *,
+                                 bands, waves: int = 0) -> list:
+        """The banded extension alignments of many device-resident long pairs, traced on the device
+        together (gsa_align_batch_band_ext_dev; synchronous): align_batch_band_dev's arguments.  One
+        dict per pair, in order, with align_pair_band_ext_dev's keys and, "kernel_ms" apart, its values
+        for that pair alone.  last_align_batch_band_ext_info() says what ran, pair by pair."""
+        n = len(pairs)
+        lo, hi = self._band_arrays(n, bands)
+        arr = (PairDev * max(n, 1))()
+        cap = 0
+        for k, (yp, ar, xp, ac) in enumerate(pairs):
+            arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+            cap += 2 * (max(ar - 1, 0) + max(ac - 1, 0)) + 1  # 2 (R + C) + 1 bytes always suffice
+        res = (AlignDbResult * max(n, 1))()
+        pinfo = (AlignBatchBandExtPair * max(n, 1))()
+        info = AlignBatchBandExtInfo()
+        ms = ctypes.c_float(0.0)
+        need = ctypes.c_int64(0)
+        buf = ctypes.create_string_buffer(max(cap, 1))
+        st = lib().gsa_align_batch_band_ext_dev(self._h, n, arr, subst_ptr, substsz, gapo,
+                                                gapo if gape is None else gape, lo, hi, int(waves), int(max_workgroups),
+                                                int(scratch_limit), res, buf, cap, ctypes.byref(need), pinfo,
+                                                ctypes.byref(info), ctypes.byref(ms), stream)
+        self._check(st, "gsa_align_batch_band_ext_dev")
+        d = {k: (float(getattr(info, k)) if t is ctypes.c_float else int(getattr(info, k)))
+             for k, t in info._fields_ if not k.startswith("pad")}
+        d["pairs"] = [{k: int(getattr(q, k)) for k, _ in q._fields_} for q in pinfo[:n]]
+        self._align_batch_band_ext_info = d
+        raw = buf.raw
+        return [{"score": int(r.score), "status": int(r.status), "i_start": int(r.i_start), "j_start": int(r.j_start),
+                 "i_end": int(r.i_end), "j_end": int(r.j_end),
+                 "cigar": raw[r.cigar_off:r.cigar_off + r.cigar_len].decode() if r.status == 0 else "",
+                 "kernel_ms": float(ms.value)} for r in res[:n]]
+
+    def last_align_batch_band_ext_info(self) -> dict:
+        """gsa_align_batch_band_ext_info of the last align_batch_band_ext_dev call on this engine:
+        last_align_batch_band_info()'s keys with "rows_used" and "cols_used" (summed over the pairs that
+        ran on the device); "pairs" lists the pairs' own values, with their "rows_used" and "cols_used"."""
+        info = getattr(self, "_align_batch_band_ext_info", None)
+        if info is None:
+            raise NwError(NwStat.errorInvalidValue, "last_align_batch_band_ext_info: no align_batch_band_ext_dev call yet")
+        d = dict(info)
+        d["pairs"] = [dict(q) for q in info["pairs"]]
+        return d
+
+    def align_batch_band_ext(self, pairs, subst, gapo: int, gape: Optional[int] = None, scratch_limit: int = 0, *,
+                             bands=None, band: Optional[int] = None, waves: int = 0, max_workgroups: int = 0) -> list:
+        """align_batch_band_ext_dev over host arrays, with the pairs and the bands as
+        score_band_ext_batch() takes them."""
+        bl = self._bands_ext_of(pairs, bands, band)
+        ptrs, dS, substsz, keep = self._upload_pairs(pairs, subst)
+        return self.align_batch_band_ext_dev(ptrs, dS, substsz, gapo, gape, max_workgroups, scratch_limit, bands=bl,
+                                             waves=waves)
 
     # -- long pairs, overlap (dovetail): scores and alignments of a batch in one call (DESIGN.md 2.2n) --
 

@@ -3,7 +3,8 @@
 // gsa_align_db_dev, gsa_align_db_multi_dev, gsa_align_pair_dev and gsa_align_batch_dev, on the K-rows and strip score kernels (nw_krow.hip, nw_strip.hip), the row scan
 // (nw_scan.hip), NW / SW from both ends (nw_bidi.hip) and the database lane kernels (nw_lanes.hip,
 // nw_lanes_multi.hip, nw_lanes_trace.hip, nw_lanes_trace_multi.hip); the banded calls
-// gsa_score_band_dev and gsa_align_pair_band_dev on nw_band.hip, their batch forms on nw_band_batch.hip.  The context
+// gsa_score_band_dev and gsa_align_pair_band_dev on nw_band.hip, their batch forms on nw_band_batch.hip,
+// the banded extension calls (gsa_*_band_ext_*) on nw_band_ext.hip and nw_band_ext_batch.hip.  The context
 // and the helpers shared with gsa_capi.hip are in gsa_ctx.h.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,8 @@
 #include "gsa_ctx.h"
 #include "nw_band.h"
 #include "nw_band_batch.h"
+#include "nw_band_ext.h"
+#include "nw_band_ext_batch.h"
 #include "nw_bidi.h"
 #include "nw_krow.h"
 #include "nw_lanes.h"
@@ -4013,38 +4016,74 @@ int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
     return GSA_SUCCESS;
 }
 
+// The info structs of the banded calls (EXT false) and of the banded extension calls (EXT true).
+template <bool EXT>
+struct BandInfoOf
+{
+    using pair = gsa_align_pair_band_info;
+    using batch_pair = gsa_align_batch_band_pair;
+    using batch = gsa_align_batch_band_info;
+};
+template <>
+struct BandInfoOf<true>
+{
+    using pair = gsa_align_pair_band_ext_info;
+    using batch_pair = gsa_align_batch_band_ext_pair;
+    using batch = gsa_align_batch_band_ext_info;
+};
+
+// An end cell the extension fill reported: inside the (trimmed) matrix and inside the band.
+inline bool band_ext_end_ok(int64_t i, int64_t j, int64_t R, int64_t C, int64_t lo, int64_t hi)
+{
+    return i >= 0 && i <= R && j >= 0 && j <= C && j - i >= lo && j - i <= hi;
+}
+
 // gsa_score_band_dev and gsa_align_pair_band_dev (align: the latter): the checks, the plan
 // (nw_band_plan.h), one fill launch of one workgroup -- with move codes when the alignment is wanted
 // and the 4 v + tag form and scratch_limit take them -- and, with codes, the walk; one copy brings the
 // score and the walk's record back, a second the move bytes.  The certificate is computed here.
 // Scratch: kBufPairMeta ([0] the result words, [64] the walk's record, [128] the pair's descriptor),
 // kBufPairCodes, kBufPairMoves.  gsa_last_launch's record is not touched.
+//
+// EXT: gsa_score_band_ext_dev and gsa_align_pair_band_ext_dev, the same steps on the
+// part of the pair the band reaches (nw_band_ext_plan.h: R, C below are R', C'; R0, C0 the whole pair),
+// with the fill that keeps the band's best cell (nw_band_ext.hip) and the walk from that cell.
+template <bool EXT>
 int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols, const int32_t* subst,
               int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo, int64_t band_hi, bool align, int64_t scratch_limit,
               gsa_score_result* sout, gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
-              gsa_align_pair_band_info* info, float* kernel_ms, hipStream_t st)
+              typename BandInfoOf<EXT>::pair* info, float* kernel_ms, hipStream_t st)
 {
     if (!ctx || !seqY || !seqX || !subst || (align ? !out : !sout)) return GSA_ERROR_INVALID_VALUE;
     int s = check_inputs(adjrows, adjcols, substsz);
     if (s != GSA_SUCCESS) return s;
     if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
     if (align && (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar))) return GSA_ERROR_INVALID_VALUE;
-    const int64_t R = adjrows - 1, C = adjcols - 1;
-    if (R >= (1ll << 30) || C >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;  // the kernel's int32 cell indices
-    if (!gsa::band_valid(R, C, band_lo, band_hi)) return GSA_ERROR_INVALID_VALUE;
-    gsa::band_clamp(R, C, &band_lo, &band_hi);
+    const int64_t R0 = adjrows - 1, C0 = adjcols - 1;
+    if (R0 >= (1ll << 30) || C0 >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;  // the kernel's int32 cell indices
+    if (!(EXT ? gsa::band_ext_valid(band_lo, band_hi) : gsa::band_valid(R0, C0, band_lo, band_hi))) return GSA_ERROR_INVALID_VALUE;
+    gsa::band_clamp(R0, C0, &band_lo, &band_hi);
+    int64_t R = R0, C = C0;
+    if (EXT) gsa::band_ext_trim(R0, C0, band_lo, band_hi, &R, &C);
     if (kernel_ms) *kernel_ms = 0.f;
     if (cigar_need) *cigar_need = 0;
-    gsa_align_pair_band_info inf;
+    typename BandInfoOf<EXT>::pair inf;
     std::memset(&inf, 0, sizeof(inf));
     inf.band_lo = band_lo;
     inf.band_hi = band_hi;
+    if constexpr (EXT)
+    {
+        inf.rows_used = R;
+        inf.cols_used = C;
+    }
     gsa_align_db_result r;
     std::memset(&r, 0, sizeof(r));
-    r.i_end = R;
-    r.j_end = C;
+    r.i_end = EXT ? 0 : R;
+    r.j_end = EXT ? 0 : C;
     std::string cig;
-    if (R == 0 || C == 0)
+    if (EXT && (R == 0 || C == 0))
+        inf.proved_optimal = 1;  // an empty side: score 0 at (0, 0), an empty CIGAR
+    else if (R == 0 || C == 0)
     {
         // one boundary, answered on the host: row 0 is E only, column 0 F only; no path leaves the band.  The
         // one gap run is held to gsa_score_dev's value range (no table value takes part: smax = 1)
@@ -4118,12 +4157,13 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
         w.hi = d.hi;
         w.rec = drec;
         w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+        w.start = EXT ? (const int*)meta : nullptr;
         // the result words and the walk's record start from zero: a kernel that wrote nothing is seen
         if ((e = hipMemsetAsync(meta, 0, 128, st)) != hipSuccess ||
             (e = hipMemcpyAsync(ddesc, &d, sizeof(d), hipMemcpyHostToDevice, st)) != hipSuccess)
             return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        if ((e = gsa::launch_band(ddesc, 1, plan.waves, subst, substsz, gapo, gape, codes, codes ? &w : nullptr, ctx->adbev,
-                                  st)) != hipSuccess)
+        if ((e = (EXT ? gsa::launch_band_ext : gsa::launch_band)(ddesc, 1, plan.waves, subst, substsz, gapo, gape, codes,
+                                                                 codes ? &w : nullptr, ctx->adbev, st)) != hipSuccess)
             return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
         note_launch(ctx);
         struct
@@ -4140,11 +4180,18 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
         if (back.res[1] != 1) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
         r.score = back.res[0];
         r.status = codes ? 0 : 1;
+        if (EXT)
+        {
+            r.i_end = back.res[2];
+            r.j_end = back.res[3];
+            if (!band_ext_end_ok(r.i_end, r.j_end, R, C, plan.lo, plan.hi) || r.score < 0)
+                return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+        }
         if (codes)
         {
             const gsa::BandWalkRec& rec = back.rec;
             // a step off the band, a record out of range, or a walk that did not end at (0, 0)
-            if (rec.offband || !rec.done || rec.n < 0 || rec.n > R + C || rec.i != 0 || rec.j != 0)
+            if (rec.offband || !rec.done || rec.n < 0 || rec.n > r.i_end + r.j_end || rec.i != 0 || rec.j != 0)
                 return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
             std::vector<unsigned char> mv((size_t)rec.n + 1);
             if (rec.n > 0 &&
@@ -4153,13 +4200,14 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
                 return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
             cig = fold_cigar(mv.data(), rec.n);
         }
-        inf.proved_optimal = gsa::band_certificate(R, C, plan.lo, plan.hi, pmax, gapo, gape, r.score);
+        inf.proved_optimal = EXT ? gsa::band_ext_certificate(R0, C0, plan.lo, plan.hi, pmax, gapo, gape, r.score)
+                                 : gsa::band_certificate(R, C, plan.lo, plan.hi, pmax, gapo, gape, r.score);
     }
     if (!align)
     {
         sout->score = r.score;
-        sout->i_end = R;
-        sout->j_end = C;
+        sout->i_end = r.i_end;
+        sout->j_end = r.j_end;
         sout->calc_kernel_ms = inf.score_ms;
         return GSA_SUCCESS;
     }
@@ -4189,11 +4237,16 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
 // [64] the round's descriptors, then its walk arguments), kBufPairBatchRec (the round's result words,
 // walk records and move bytes, copied back as one), kBufPairCodes.  gsa_last_launch's record is not
 // touched.
+//
+// EXT: gsa_score_band_ext_batch_dev and gsa_align_batch_band_ext_dev, as band_impl<true>
+// does it per pair: the trimmed pair (b.R, b.C; b.R0, b.C0 the whole one), four result words per pair,
+// nw_band_ext_batch.hip's launches, the walks from the end cells.
+template <bool EXT>
 int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                     int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
                     int32_t max_workgroups, bool align, int64_t scratch_limit, gsa_score_result* sout, gsa_align_db_result* out,
-                    char* cigar, int64_t cigar_cap, int64_t* cigar_need, gsa_align_batch_band_pair* pair_info,
-                    gsa_align_batch_band_info* info, float* kernel_ms, hipStream_t st)
+                    char* cigar, int64_t cigar_cap, int64_t* cigar_need, typename BandInfoOf<EXT>::batch_pair* pair_info,
+                    typename BandInfoOf<EXT>::batch* info, float* kernel_ms, hipStream_t st)
 {
     if (!ctx || npairs < 0 || !pairs || !subst || !band_lo || !band_hi || (align ? !out : !sout)) return GSA_ERROR_INVALID_VALUE;
     if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
@@ -4202,7 +4255,7 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
     if (align && (scratch_limit < 0 || cigar_cap < 0 || (cigar_cap > 0 && !cigar))) return GSA_ERROR_INVALID_VALUE;
     struct Bp
     {
-        int64_t R, C;
+        int64_t R, C, R0, C0;
         gsa::BandPlan plan;  // (lo, hi: also of a pair with an empty side)
         bool host, codes;
     };
@@ -4216,8 +4269,11 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         b.C = pairs[p].adjcols - 1;
         if (b.R >= (1ll << 30) || b.C >= (1ll << 30)) return GSA_ERROR_INVALID_VALUE;  // the kernel's int32 cell indices
         int64_t lo = band_lo[p], hi = band_hi[p];
-        if (!gsa::band_valid(b.R, b.C, lo, hi)) return GSA_ERROR_INVALID_VALUE;
+        if (!(EXT ? gsa::band_ext_valid(lo, hi) : gsa::band_valid(b.R, b.C, lo, hi))) return GSA_ERROR_INVALID_VALUE;
         gsa::band_clamp(b.R, b.C, &lo, &hi);
+        b.R0 = b.R;
+        b.C0 = b.C;
+        if (EXT) gsa::band_ext_trim(b.R0, b.C0, lo, hi, &b.R, &b.C);
         b.host = b.R == 0 || b.C == 0;
         b.codes = false;
         if (b.host)
@@ -4225,7 +4281,7 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
             b.plan.lo = lo;
             b.plan.hi = hi;
             bool stripOk = false;
-            if (b.R + b.C > 0 && score_ranges(b.R, b.C, 1, gapo, gape, 0, &stripOk) != GSA_SUCCESS) return GSA_ERROR_INVALID_VALUE;
+            if (!EXT && b.R + b.C > 0 && score_ranges(b.R, b.C, 1, gapo, gape, 0, &stripOk) != GSA_SUCCESS) return GSA_ERROR_INVALID_VALUE;
         }
         else
         {
@@ -4261,7 +4317,7 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
     // every pair passed: from here on the call answers
     if (kernel_ms) *kernel_ms = 0.f;
     if (cigar_need) *cigar_need = 0;
-    gsa_align_batch_band_info inf;
+    typename BandInfoOf<EXT>::batch inf;
     std::memset(&inf, 0, sizeof(inf));
     std::vector<gsa_align_db_result> res((size_t)npairs);
     if (npairs > 0) std::memset(res.data(), 0, res.size() * sizeof(gsa_align_db_result));
@@ -4273,13 +4329,18 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
     {
         const Bp& b = bp[(size_t)p];
         gsa_align_db_result& r = res[(size_t)p];
-        r.i_end = b.R;
-        r.j_end = b.C;
+        r.i_end = EXT ? 0 : b.R;
+        r.j_end = EXT ? 0 : b.C;
+        if constexpr (EXT)
+        {
+            inf.rows_used += b.host ? 0 : b.R;
+            inf.cols_used += b.host ? 0 : b.C;
+        }
         if (b.host)
         {
             // one boundary, answered on the host as band_impl does: row 0 is E only, column 0 F only
             const int64_t k = b.R + b.C;
-            if (k > 0)
+            if (!EXT && k > 0)
             {
                 r.score = (int32_t)(gapo + (k - 1) * gape);
                 cig[(size_t)p] = std::to_string(k) + (b.R > 0 ? 'I' : 'D');
@@ -4330,7 +4391,8 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         // the device tables: [counter | descriptors | walk arguments] and [result words | records | moves]
         const size_t descOff = 64, walkOff = descOff + ((n * sizeof(gsa::BandDesc) + 63) & ~(size_t)63);
         const size_t tabBytes = walkOff + (codes ? n * sizeof(gsa::BandWalkArgs) : 0);
-        const size_t recOff = (n * 8 + 63) & ~(size_t)63, movOff = recOff + (codes ? n * sizeof(gsa::BandWalkRec) : 0);
+        constexpr size_t kWords = EXT ? 4 : 2;  // result words of a pair
+        const size_t recOff = (n * kWords * 4 + 63) & ~(size_t)63, movOff = recOff + (codes ? n * sizeof(gsa::BandWalkRec) : 0);
         std::vector<int64_t> mvAt(n, 0), cdAt(n, 0);
         int64_t movTotal = 0, codeTotal = 0;
         if (codes)
@@ -4360,7 +4422,7 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
             d.seqY = pairs[p].seqY;
             d.seqX = pairs[p].seqX;
             d.codes = codes ? dcodes + cdAt[k] : nullptr;
-            d.result = (int*)drec + 2 * k;
+            d.result = (int*)drec + kWords * k;
             d.stripBytes = b.plan.stripBytes;
             d.R = (int)b.R;
             d.C = (int)b.C;
@@ -4384,19 +4446,20 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
             w.hi = d.hi;
             w.rec = (gsa::BandWalkRec*)(drec + recOff) + k;
             w.moves = (unsigned char*)drec + movOff + mvAt[k];
+            w.start = EXT ? d.result : nullptr;
             std::memcpy(blob.data() + walkOff + k * sizeof(w), &w, sizeof(w));
         }
         int grid = 0, walkGrid = (int)std::min<size_t>(n, 65535);
         if (max_workgroups > 0) walkGrid = std::min(walkGrid, (int)max_workgroups);
-        if ((e = gsa::band_batch_fill_grid(gapo != gape, codes, nwv, (int)n, max_workgroups, &grid)) != hipSuccess)
+        if ((e = (EXT ? gsa::band_ext_batch_fill_grid : gsa::band_batch_fill_grid)(gapo != gape, codes, nwv, (int)n, max_workgroups, &grid)) != hipSuccess)
             return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
         // the result words and the walks' records start from zero: a kernel that wrote nothing is seen
         if ((e = hipMemsetAsync(drec, 0, movOff, st)) != hipSuccess ||
             (e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
             return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        if ((e = gsa::launch_band_batch((const gsa::BandDesc*)(dtab + descOff), (int)n, (unsigned*)dtab, nwv, grid, subst, substsz,
-                                        gapo, gape, codes, codes ? (const gsa::BandWalkArgs*)(dtab + walkOff) : nullptr, walkGrid,
-                                        ctx->adbev, st)) != hipSuccess)
+        if ((e = (EXT ? gsa::launch_band_ext_batch : gsa::launch_band_batch)(
+                 (const gsa::BandDesc*)(dtab + descOff), (int)n, (unsigned*)dtab, nwv, grid, subst, substsz, gapo, gape, codes,
+                 codes ? (const gsa::BandWalkArgs*)(dtab + walkOff) : nullptr, walkGrid, ctx->adbev, st)) != hipSuccess)
             return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
         note_launch(ctx);
         back.resize(movOff + (size_t)movTotal);
@@ -4413,14 +4476,22 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         {
             const int p = members[(size_t)order[k]];
             const Bp& b = bp[(size_t)p];
-            if (words[2 * k + 1] != 1) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            res[(size_t)p].score = words[2 * k];
+            if (words[kWords * k + 1] != 1) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            gsa_align_db_result& r = res[(size_t)p];
+            r.score = words[kWords * k];
+            if (EXT)
+            {
+                r.i_end = words[kWords * k + 2];
+                r.j_end = words[kWords * k + 3];
+                if (!band_ext_end_ok(r.i_end, r.j_end, b.R, b.C, b.plan.lo, b.plan.hi) || r.score < 0)
+                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+            }
             if (!codes) continue;
             roundOf[(size_t)p] = (int)l - 1;
             gsa::BandWalkRec rec;
             std::memcpy(&rec, back.data() + recOff + k * sizeof(rec), sizeof(rec));
             // a step off the band, a record out of range, or a walk that did not end at (0, 0)
-            if (rec.offband || !rec.done || rec.n < 0 || rec.n > b.R + b.C || rec.i != 0 || rec.j != 0)
+            if (rec.offband || !rec.done || rec.n < 0 || rec.n > r.i_end + r.j_end || rec.i != 0 || rec.j != 0)
                 return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
             cig[(size_t)p] = fold_cigar((const unsigned char*)back.data() + movOff + mvAt[k], rec.n);
         }
@@ -4431,8 +4502,8 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         for (int p = 0; p < npairs; ++p)
         {
             sout[p].score = res[(size_t)p].score;
-            sout[p].i_end = bp[(size_t)p].R;
-            sout[p].j_end = bp[(size_t)p].C;
+            sout[p].i_end = res[(size_t)p].i_end;
+            sout[p].j_end = res[(size_t)p].j_end;
             sout[p].calc_kernel_ms = 0.f;
         }
         if (kernel_ms) *kernel_ms = inf.nocode_ms;
@@ -4459,18 +4530,24 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         out[p] = r;
         if (pair_info)
         {
-            gsa_align_batch_band_pair& pi = pair_info[p];
+            typename BandInfoOf<EXT>::batch_pair& pi = pair_info[p];
             std::memset(&pi, 0, sizeof(pi));
             pi.band_lo = b.plan.lo;
             pi.band_hi = b.plan.hi;
             pi.round = roundOf[(size_t)p];
             pi.proved_optimal = 1;
+            if constexpr (EXT)
+            {
+                pi.rows_used = b.R;
+                pi.cols_used = b.C;
+            }
             if (!b.host)
             {
                 pi.code_bytes = b.plan.codeBytes;
                 pi.strips = (int32_t)b.plan.strips;
                 pi.supersteps = (int32_t)b.plan.T;
-                pi.proved_optimal = gsa::band_certificate(b.R, b.C, b.plan.lo, b.plan.hi, pmax, gapo, gape, r.score);
+                pi.proved_optimal = EXT ? gsa::band_ext_certificate(b.R0, b.C0, b.plan.lo, b.plan.hi, pmax, gapo, gape, r.score)
+                                        : gsa::band_certificate(b.R, b.C, b.plan.lo, b.plan.hi, pmax, gapo, gape, r.score);
             }
         }
     }
@@ -4491,7 +4568,7 @@ int gsa_score_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const
                        gsa_score_result* out, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return band_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, false, 0, out, nullptr,
+    return band_impl<false>(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, false, 0, out, nullptr,
                      nullptr, 0, nullptr, nullptr, nullptr, pick_stream(ctx, stream));
 }
 
@@ -4501,7 +4578,7 @@ int gsa_align_pair_band_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
                             gsa_align_pair_band_info* info, float* kernel_ms, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return band_impl(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, true, scratch_limit,
+    return band_impl<false>(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, true, scratch_limit,
                      nullptr, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
 }
 
@@ -4510,7 +4587,7 @@ int gsa_score_band_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
                              int32_t max_workgroups, gsa_score_result* out, float* batch_kernel_ms, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return band_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, false, 0, out,
+    return band_batch_impl<false>(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, false, 0, out,
                            nullptr, nullptr, 0, nullptr, nullptr, nullptr, batch_kernel_ms, pick_stream(ctx, stream));
 }
 
@@ -4521,9 +4598,49 @@ int gsa_align_batch_band_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
                              gsa_align_batch_band_info* info, float* kernel_ms, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return band_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, true,
+    return band_batch_impl<false>(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, true,
                            scratch_limit, nullptr, out, cigar, cigar_cap, cigar_need, pair_info, info, kernel_ms,
                            pick_stream(ctx, stream));
+}
+
+int gsa_score_band_ext_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                           const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo, int64_t band_hi,
+                           gsa_score_result* out, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_impl<true>(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, false, 0, out, nullptr,
+                           nullptr, 0, nullptr, nullptr, nullptr, pick_stream(ctx, stream));
+}
+
+int gsa_align_pair_band_ext_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                                const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo,
+                                int64_t band_hi, int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap,
+                                int64_t* cigar_need, gsa_align_pair_band_ext_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_impl<true>(ctx, seqY, adjrows, seqX, adjcols, subst, substsz, gapo, gape, band_lo, band_hi, true, scratch_limit,
+                           nullptr, out, cigar, cigar_cap, cigar_need, info, kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_score_band_ext_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                                 int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
+                                 int32_t max_workgroups, gsa_score_result* out, float* batch_kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_batch_impl<true>(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, false, 0,
+                                 out, nullptr, nullptr, 0, nullptr, nullptr, nullptr, batch_kernel_ms, pick_stream(ctx, stream));
+}
+
+int gsa_align_batch_band_ext_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
+                                 int32_t gapo, int32_t gape, const int64_t* band_lo, const int64_t* band_hi, int32_t waves,
+                                 int32_t max_workgroups, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                                 int64_t cigar_cap, int64_t* cigar_need, gsa_align_batch_band_ext_pair* pair_info,
+                                 gsa_align_batch_band_ext_info* info, float* kernel_ms, void* stream)
+{
+    if (!ctx) return GSA_ERROR_INVALID_VALUE;
+    return band_batch_impl<true>(ctx, npairs, pairs, subst, substsz, gapo, gape, band_lo, band_hi, waves, max_workgroups, true,
+                                 scratch_limit, nullptr, out, cigar, cigar_cap, cigar_need, pair_info, info, kernel_ms,
+                                 pick_stream(ctx, stream));
 }
 
 int gsa_align_batch_overlap_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,

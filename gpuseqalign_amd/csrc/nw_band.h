@@ -15,7 +15,8 @@ struct BandDesc
     const int* seqY;       // rows, letters at 1 ... R
     const int* seqX;       // columns, letters at 1 ... C
     unsigned char* codes;  // strip s at s stripBytes, column j at (j - o(s)) TR / 2, lane l at l KR / 2
-    int* result;           // [0] H(R, C), [1] 1 once it is written
+    int* result;           // [0] H(R, C), [1] 1 once it is written; the extension fill (nw_band_ext.h): [0] the
+                           // best H of the band, [1] 1 once written, [2] i_end, [3] j_end
     long long stripBytes;
     int R, C;
     int lo, hi;            // the clamped band
@@ -41,6 +42,7 @@ struct BandWalkArgs
     int R, C, lo, hi;
     BandWalkRec* rec;
     unsigned char* moves;  // one byte per move, last move first
+    const int* start;      // null: the walk starts at (R, C); else at (start[2], start[3]), an extension fill's result words
 };
 
 // The fill of npairs pairs, one workgroup of `waves` waves each, with (codes) or without move codes;

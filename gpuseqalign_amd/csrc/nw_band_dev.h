@@ -1,11 +1,14 @@
 // nw_band_dev.h -- the device code the banded kernels share: the table load, the
 // lockstep super-steps of one pair on one workgroup, and the one-lane walk.  Included by nw_band.hip
 // (one pair per workgroup of the grid) and by nw_band_batch.hip (a persistent grid whose workgroups
-// claim pair after pair), so that both run the same body.
+// claim pair after pair), so that both run the same body; nw_band_ext.hip and nw_band_ext_batch.hip run
+// it in the extension mode (EXT).
 //
-// band_pair_fill sets every piece of per-strip state (s, Hp, E, hdiag, fLast, let, xnext, yo) anew
-// when it is entered and ends every super-step, the last one included, with __syncthreads(): a
-// workgroup may run it for one pair after another on the same ring.  The ring holds
+// band_pair_fill sets every piece of per-strip state (s, Hp, E, hdiag, fLast, let, xnext, yo, and the
+// extension mode's best values) anew when it is entered and ends every super-step, the last one
+// included, with __syncthreads(): a workgroup may run it for one pair after another on the same ring,
+// and in the extension mode on the same slots, if a barrier of the caller's stands between the pairs
+// (thread 0 reads the slots last).  The ring holds
 // (blockDim.x / 64) x kBandRingBlocks x 64 int2 and is passed in, so that a caller may size it by its
 // waves.  No loop here polls anything: the fill's are bounded by T, 64 and KR, the walk's by R + C.
 #pragma once
@@ -43,9 +46,29 @@ __device__ __forceinline__ void band_load_tab(int* tab, const int* subst, int ss
     }
 }
 
+// A candidate end cell of the extension mode: the larger value wins, of equal values the smaller row
+// (two lanes, or two waves, never hold the same row, so the column need not decide).
+__device__ __forceinline__ void best_take(int& v, int& i, int& j, int ov, int oi, int oj)
+{
+    const bool take = ov > v || (ov == v && oi < i);
+    v = take ? ov : v;
+    i = take ? oi : i;
+    j = take ? oj : j;
+}
+
 // The super-steps of pair d, by all threads of the workgroup.  ring: [wave][RQ][64].
-template <bool AFFINE, bool CODES>
-__device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab, int2* ring, int ssz, int go, int ge)
+//
+// EXT (the extension mode, nw_band_ext.hip): the result is the largest H of the band
+// and its first cell in row-major order, not H(R, C), and the band need not hold (R, C).  A lane keeps
+// the best value of each of its KR rows with its column (strict >: columns ascend, so the first column
+// of a row wins), folds them at the strip's last super-step into its running (value, i, j) (strict >:
+// rows and the strips of a wave ascend), and behind the last super-step's barrier the lanes of a wave
+// reduce theirs by shuffles, every wave writes one slot of `best` ([waves] int4 of LDS, the caller's),
+// and behind one more barrier thread 0 takes the best slot and writes the four result words.  Values
+// start from (0, (0, 0)): H(0, 0) = 0 is first in row-major order and no border cell exceeds it.
+template <bool AFFINE, bool CODES, bool EXT = false>
+__device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab, int2* ring, int ssz, int go, int ge,
+                                               int4* best = nullptr)
 {
     constexpr int SC = CODES ? 4 : 1;             // values are kept as SC v (+ tag)
     constexpr int NEG = -(1 << 29);               // minus infinity: SC x -2^27 with codes, -2^29 without
@@ -62,12 +85,16 @@ __device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab
     int s = wave;  // the strip this wave runs, or runs next
     int yo[KR], Hp[KR], E[KR];
     int hdiag = NEG, fLast = NEGF, let = 0, xnext = 0;
+    int bv[KR], bj[KR];            // EXT: the best value (as SC v) of each row of the strip, and its column
+    int rv = 0, ri = 0, rj = 0;    // EXT: the lane's best over the strips it has finished
 #pragma unroll
     for (int k = 0; k < KR; ++k)
     {
         yo[k] = 0;
         Hp[k] = NEG;
         E[k] = NEG;
+        bv[k] = 0;
+        bj[k] = 0;
     }
 
     for (int g = 0; g < d.T; ++g)
@@ -87,6 +114,11 @@ __device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab
                     yo[k] = d.seqY[min(i0 + 1 + k, R)];
                     Hp[k] = NEG;
                     E[k] = NEG;
+                    if (EXT)
+                    {
+                        bv[k] = 0;
+                        bj[k] = 0;
+                    }
                 }
                 // the cell above lane 0's first one, (iT, o - 1), lies on the band's lowest diagonal: the
                 // producer's step 64 KR + 62.  The lanes below overwrite theirs before their first cell.
@@ -186,6 +218,13 @@ __device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab
                             h &= ~3;
                         }
                         h = ok ? h : NEG;
+                        if (EXT)
+                        {
+                            // (a cell off the band holds NEG and never wins; with codes h is 4 v here)
+                            const bool better = h > bv[k];
+                            bv[k] = better ? h : bv[k];
+                            bj[k] = better ? j : bj[k];
+                        }
                         if (AFFINE)
                         {
                             E[k] = ok ? e : NEG;
@@ -206,7 +245,7 @@ __device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab
                 }
                 hdiag = hu0;
                 if (lane == 63) ringOwn[(g % RQ) * 64 + u] = make_int2(Hp[KR - 1], fLast);
-                if (j == C && rowsLeft >= 0 && rowsLeft < KR)
+                if (!EXT && j == C && rowsLeft >= 0 && rowsLeft < KR)
                 {
                     int h = 0;
 #pragma unroll
@@ -215,9 +254,41 @@ __device__ __forceinline__ void band_pair_fill(const BandDesc& d, const int* tab
                     d.result[1] = 1;
                 }
             }
+            if (EXT && q == d.nq - 1)
+            {
+#pragma unroll
+                for (int k = 0; k < KR; ++k)
+                {
+                    const bool better = bv[k] > rv;
+                    rv = better ? bv[k] : rv;
+                    ri = better ? i0 + 1 + k : ri;
+                    rj = better ? bj[k] : rj;
+                }
+            }
             if (q == d.nq - 1) s += nwv;
         }
         __syncthreads();
+    }
+    if (EXT)
+    {
+        // every strip is folded (the barrier above ended the last super-step): lanes, then waves
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+            best_take(rv, ri, rj, __shfl_xor(rv, off, 64), __shfl_xor(ri, off, 64), __shfl_xor(rj, off, 64));
+        if (lane == 0) best[wave] = make_int4(rv, ri, rj, 0);
+        __syncthreads();
+        if (threadIdx.x == 0)
+        {
+            for (int w = 1; w < nwv; ++w)
+            {
+                const int4 o = best[w];
+                best_take(rv, ri, rj, o.x, o.y, o.z);
+            }
+            d.result[0] = CODES ? rv >> 2 : rv;
+            d.result[2] = ri;
+            d.result[3] = rj;
+            d.result[1] = 1;
+        }
     }
 }
 
@@ -228,7 +299,8 @@ __device__ __forceinline__ void band_walk(const BandWalkArgs& a)
     const int* const x = a.seqX;
     const int* const y = a.seqY;
     unsigned char* const mv = a.moves;
-    int i = a.R, j = a.C, n = 0;
+    // the extension mode's walk starts on the end cell its fill found, behind it on the stream
+    int i = a.start ? a.start[2] : a.R, j = a.start ? a.start[3] : a.C, n = 0;
     unsigned state = kWalkH;
     bool done = false, off = false;
     while (!done && !off)
@@ -272,6 +344,27 @@ __device__ __forceinline__ void band_walk(const BandWalkArgs& a)
     o.offband = off ? 1 : 0;
     o.pad0 = o.pad1 = 0;
     *a.rec = o;
+}
+
+// The extension mode's walk (a.start is not null): a start cell outside the matrix is reported as off
+// the band before any code is read; else band_walk.
+__device__ __forceinline__ void band_walk_from_start(const BandWalkArgs& a)
+{
+    const int i = a.start[2], j = a.start[3];
+    if (i < 0 || j < 0 || i > a.R || j > a.C)
+    {
+        BandWalkRec o;
+        o.i = i;
+        o.j = j;
+        o.state = kWalkH;
+        o.n = 0;
+        o.done = 0;
+        o.offband = 1;
+        o.pad0 = o.pad1 = 0;
+        *a.rec = o;
+        return;
+    }
+    band_walk(a);
 }
 
 }  // namespace band_dev

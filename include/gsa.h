@@ -1361,6 +1361,129 @@ int gsa_align_batch_band_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
                              gsa_align_batch_band_pair* pair_info, gsa_align_batch_band_info* info, float* kernel_ms,
                              void* stream);
 
+/* Long pairs, banded extension: the start fixed at (0, 0), the end free -- the best cell of the band; one
+ * pair and a batch.  The step every seed-and-extend pipeline runs behind its outermost
+ * anchor: the global banded call would drag the unrelated tails into the CIGAR, the local mode would
+ * lose the anchor.  (Left extension: the caller reverses both sequences.)
+ *
+ * Semantics.  seqY, seqX, the table and gapo <= gape <= 0 as gsa_score_band_dev takes them.
+ * The band is a pair band_lo <= band_hi of diagonals j - i.  Cell (i, j), 0 <= i <= R, 0 <= j <= C, is
+ * in the band iff band_lo <= j - i <= band_hi; outside the band H = E = F = minus infinity.
+ *   Values: exactly gsa_align_pair_band_dev's.  H(0, 0) = 0, row 0 is E only, column 0 is F only, the
+ *   Gotoh recurrences inside.
+ *   Validity: the band must hold (0, 0): band_lo <= 0 <= band_hi, else errorInvalidValue.  It need not
+ *   hold (R, C).  The call clamps band_lo to -R and band_hi to C; the width after clamping must be at
+ *   most gsa_band_max_width().
+ *   Score: the maximum of H over all cells of the band.  It is never negative, since H(0, 0) = 0.
+ *   End cell: the first maximal cell in row-major order (smallest i, then smallest j), the local
+ *   mode's rule.  A score of 0 therefore ends at (0, 0) with an empty CIGAR and status 0; border cells
+ *   other than (0, 0) never win.
+ *   Alignment: the start cell is (0, 0).  Walk from the end cell in state H: diagonal before F before
+ *   E; a gap is extended only when that is strictly better than opening.  CIGAR letters = X I D; the
+ *   CIGAR consumes exactly i_end letters of seqY and j_end letters of seqX.
+ *   R = 0 or C = 0 is answered on the host: score 0, end (0, 0), an empty CIGAR, status 0,
+ *   proved_optimal 1.
+ * Trimming.  Rows beyond C - band_lo and columns beyond R + band_hi hold no cell of the band.  The call
+ * plans, launches and guards its value ranges on R' = min(R, C - band_lo), C' = min(C, R + band_hi)
+ * (clamped band), and reports them as rows_used and cols_used; the result is that of the whole pair.
+ * The certificate (proved_optimal).  Let pmax = max(0, largest table value), S the banded score, and
+ * band_lo, band_hi the clamped values.
+ *   A path that leaves the band on the high side holds at least band_hi + 1 letters of D.  No cell of
+ *   it behind that scores more than
+ *     U_hi = pmax min(R, C - band_hi - 1) + gapo + band_hi gape.
+ *   This applies only if band_hi < C.
+ *   On the low side, with a = 1 - band_lo,
+ *     U_lo = pmax min(C, R - a) + gapo + (a - 1) gape.
+ *   This applies only if band_lo > -R.
+ *   proved_optimal = 1 iff S is strictly greater than every bound that applies.
+ *   Then the score, both cells and the CIGAR are those of the unbanded extension (the band -R ... C).
+ *
+ * How (nw_band_ext.hip, nw_band_ext_batch.hip): gsa_score_band_dev's workgroup, strips, super-steps and
+ * ring, the same device body with one addition.  Every lane keeps the best value and its column for
+ * each of its 4 rows (one compare and two selects per cell), folds them at the end of a strip, and
+ * behind the last super-step the lanes reduce by shuffles, the waves through one LDS slot each behind
+ * one barrier.  Nothing polls memory and the reduction uses no atomics.  The fill writes score and end
+ * cell into its result words, and the walk -- enqueued behind it -- starts where they say.
+ *
+ * gsa_score_band_ext_dev fills gsa_score_dev's result struct: score, end cell, the hipEvent time of the
+ * fill.  Refusals, all errorInvalidValue before anything is enqueued: everything gsa_score_band_dev
+ * refuses, with its validity rule replaced by the one above and the value range B taken on (R', C').
+ * Not here: X-drop or Z-drop termination, the best score at the query's end, left extension.  The
+ * calls add no launch kind and no knob, leave the record of gsa_last_launch and the fills' sticky error
+ * word alone, and count their scratch (the global banded calls' buffers) in gsa_mem_stats. */
+int gsa_score_band_ext_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                           const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo,
+                           int64_t band_hi, gsa_score_result* out, void* stream);
+
+typedef struct gsa_align_pair_band_ext_info {  /* gsa_align_pair_band_info's fields, of the trimmed pair */
+    int32_t strip_rows;      /* TR: rows of a strip (256) */
+    int32_t strips;          /* strips that hold the rows 1 ... R' */
+    int32_t waves;           /* waves of the workgroup */
+    int32_t supersteps;      /* T: barriers of the workgroup */
+    int32_t proved_optimal;  /* the certificate above */
+    int32_t pad0;
+    int64_t band_lo, band_hi; /* the clamped band */
+    int64_t code_bytes;      /* bytes of move codes of the band (also when they exceed scratch_limit) */
+    float score_ms, walk_ms; /* hipEvent time of the fill and of the walk */
+    int64_t rows_used, cols_used; /* R', C': the part of the pair the band reaches */
+} gsa_align_pair_band_ext_info;
+
+/* The banded extension alignment of one long pair, traced on the device: gsa_align_pair_band_dev's
+ * arguments, buffers and rules for scratch_limit, cigar_cap, cigar_need and status.  Status 1 (no codes
+ * were kept: B on (R', C') reaches 2^26, or code_bytes exceeds scratch_limit): score and end cell are
+ * still returned, the CIGAR is empty.  Status 2: the CIGAR does not fit.  The walk's record is
+ * validated on the host: not off the band, ended at (0, 0), at most i_end + j_end moves; the end cell
+ * inside the trimmed matrix and inside the band; else errorKernelFailure. */
+int gsa_align_pair_band_ext_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
+                                const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t band_lo,
+                                int64_t band_hi, int64_t scratch_limit, gsa_align_db_result* out, char* cigar,
+                                int64_t cigar_cap, int64_t* cigar_need, gsa_align_pair_band_ext_info* info,
+                                float* kernel_ms, void* stream);
+
+/* The scores of a batch: gsa_score_band_batch_dev's arguments, persistent grid, waves rule and refusals.
+ * out[p] is exactly what gsa_score_band_ext_dev returns for pair p alone (calc_kernel_ms 0), whatever
+ * its position, its neighbours, the waves or the grid. */
+int gsa_score_band_ext_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                                 int32_t substsz, int32_t gapo, int32_t gape, const int64_t* band_lo,
+                                 const int64_t* band_hi, int32_t waves, int32_t max_workgroups, gsa_score_result* out,
+                                 float* batch_kernel_ms, void* stream);
+
+typedef struct gsa_align_batch_band_ext_pair {  /* one pair of the batch: gsa_align_pair_band_ext_info's values */
+    int64_t band_lo, band_hi; /* the clamped band */
+    int64_t code_bytes;       /* bytes of move codes of the pair's band (also when it got none) */
+    int64_t rows_used, cols_used; /* R', C' of the pair */
+    int32_t strips;           /* strips that hold the rows 1 ... R' (0: answered on the host) */
+    int32_t supersteps;       /* T of the pair */
+    int32_t proved_optimal;   /* the certificate of gsa_align_pair_band_ext_dev */
+    int32_t round;            /* >= 0: the fill + walk round the pair ran in; -1: answered on the host;
+                                 -2: it ran without codes (status 1) */
+} gsa_align_batch_band_ext_pair;
+
+typedef struct gsa_align_batch_band_ext_info {  /* gsa_align_batch_band_info's fields */
+    int32_t batch_pairs;   /* pairs traced on the device */
+    int32_t host_pairs;    /* pairs answered on the host: an empty side */
+    int32_t nocode_pairs;  /* pairs that ran without codes: status 1 */
+    int32_t rounds;        /* fill + walk launch pairs */
+    int32_t waves;         /* waves per workgroup the launches used (the largest, when they differ) */
+    int32_t strip_rows;    /* TR: rows of a strip (256); 0: nothing was launched */
+    int64_t code_bytes;    /* peak bytes of move codes held at once */
+    float fill_ms, nocode_ms, walk_ms; /* hipEvent time of the fills with codes, of the launch without and of
+                                          the walks, summed over the rounds */
+    int32_t pad0;
+    int64_t rows_used, cols_used; /* R' and C' summed over the pairs that ran on the device */
+} gsa_align_batch_band_ext_info;
+
+/* The alignments of a batch: gsa_align_batch_band_dev's arguments, rounds, CIGAR buffer and refusals.
+ * out[p] is, field for field, what gsa_align_pair_band_ext_dev returns for pair p alone, and
+ * pair_info[p] its info values, whatever the pair's position, its neighbours, the waves, the grid or the
+ * round.  Nothing is enqueued before every pair has passed its checks. */
+int gsa_align_batch_band_ext_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
+                                 int32_t substsz, int32_t gapo, int32_t gape, const int64_t* band_lo,
+                                 const int64_t* band_hi, int32_t waves, int32_t max_workgroups, int64_t scratch_limit,
+                                 gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
+                                 gsa_align_batch_band_ext_pair* pair_info, gsa_align_batch_band_ext_info* info,
+                                 float* kernel_ms, void* stream);
+
 /* Host buffers (alloc, copy in, fill, laps as gsa_align_*). */
 int gsa_score(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
               const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
