@@ -2,77 +2,31 @@
 // (gsa_align_pair_overlap_dev): a suffix of either sequence against a prefix of the
 // other, or either within the other, traced on the device from the score launch's checkpoint rows.
 //
-// The fill and the walk are nw_pair_trace.hip's global ones (one wave per strip of TR rows, lane l on
-// the rows l KR + 1 ... (l + 1) KR one column behind lane l - 1, the 4-bit codes of nw_lanes_trace.hip
-// from the tagged maximum over 4 v + tag, the table in LDS), kept here as a copy of their own so that
-// that unit's and the semi-global unit's kernels stay as they are.  The differences:
-//   the row above strip 0 is the free row 0: H = 0, F = minus infinity at every column;
-//   column 0 is free as well: H = 0, E = F = minus infinity in every row -- set here from the
-//   definition, not read from the score launch, whose F on column 0 is folded into a floor;
-//   only the rows 1 ... i_end are filled, over the columns 1 ... J, the codes of column j at (j - 1) TR / 2;
-//   the walk stops as soon as it stands on row 0 or on column 0 and emits no letter along either.
+// The strip fill and the walk are nw_pair_trace_dev.h's.  A fill task is a ticket t of the chunk's atomic
+// counter: strip tLo + t of the one pair in the arguments, its codes at t stripBytes.  The border is
+// kOverlap: the row above strip 0 is the free row 0 (H = 0, F = minus infinity), and column 0 is free as
+// well (H = 0, E = F = minus infinity in every row) -- set from the definition, not read from the score
+// launch, whose F on column 0 is folded into a floor; only the rows 1 ... i_end are filled, and row
+// letters clamp to i_end.
 #include "nw_pair_overlap_trace.h"
 
-#include <algorithm>
-
-#include "nw_lanes_trace.h"
-#include "nw_strip.h"
+#include "nw_pair_trace_dev.h"
 
 namespace gsa {
 
 namespace {
 
-constexpr int kNegQ = -(1 << 29);  // 4 x "minus infinity" (-2^27), tag 0
-constexpr unsigned kWalkH = 4u;    // the walk's state H; inside a gap the state is the gap's source code
-constexpr int kFillWgsPerCu = 8;
-
-__device__ __forceinline__ int from_lane_above(int own, int src)
-{
-    // wave_shr:1 over the 64 lanes; lane 0 has no source and keeps `own`
-    return __builtin_amdgcn_update_dpp(own, src, 0x138, 0xf, 0xf, false);
-}
-
-template <int N>
-struct __attribute__((aligned(4 * N))) CodesN
-{
-    unsigned w[N];
-};
-
-// The checkpoint row above strip s at column j, as 4 H (tag 0) and 4 F | F's tag: the low 32 bits of
-// the granule, signed, H = Hgo' - (go - ge) + (i + j) ge, F = F' + (i + j) ge.
-template <bool AFFINE>
-__device__ __forceinline__ int2 checkpoint(const unsigned long long* gh, const unsigned long long* gf, int j, int iT,
-                                           int go, int ge)
-{
-    const int sh = (iT + j) * ge;
-    const int h = (int)(unsigned)gh[j] - (go - ge) + sh;
-    int2 r;
-    r.x = 4 * h;
-    r.y = AFFINE ? ((4 * ((int)(unsigned)gf[j] + sh)) | (int)kDbTraceF) : 0;
-    return r;
-}
+using namespace pair_dev;
 
 template <bool AFFINE, int KR>
 __global__ __launch_bounds__(64) void nw_overlap_fill_kernel(OverlapFillArgs a)
 {
-    constexpr int TR = 64 * KR;
-    constexpr int NW = KR / 8;  // dwords of codes per lane and column
     __shared__ int tab[32 * 32];
     const int ssz = a.substsz;
-    // tab[x letter][y letter] = 4 s(y, x) + tag "diagonal"
-    for (int idx = threadIdx.x; idx < ssz * ssz; idx += 64)
-    {
-        const int xl = idx / ssz, yl = idx - xl * ssz;
-        tab[idx] = 4 * a.subst[yl * ssz + xl] + (int)kDbTraceDiag;
-    }
+    load_tab(tab, a.subst, ssz);
     __syncthreads();
 
     const int lane = threadIdx.x;
-    const int go = a.go, ge = a.ge;
-    const int go4 = 4 * go, ge4 = 4 * ge;
-    const int W = a.J;  // the columns 1 ... W
-    const int* const x = a.seqX;
-
     for (;;)
     {
         unsigned t = 0;
@@ -80,171 +34,34 @@ __global__ __launch_bounds__(64) void nw_overlap_fill_kernel(OverlapFillArgs a)
         t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
         if (t >= (unsigned)a.nstrips) break;
         const int s = a.tLo + (int)t;
-        const int iT = s * TR;              // the checkpoint row (0: the free row)
-        const int i0 = iT + lane * KR;      // this lane's rows: i0 + 1 ... i0 + KR
-        const int J = i0 < a.iEnd ? W : 0;  // lanes wholly below i_end have no cells
-        const bool ck = s > 0 && lane == 0;
-        const unsigned long long* const gh = a.gran + (size_t)(s > 0 ? s - 1 : 0) * (size_t)a.granStride;
-        const unsigned long long* const gf = a.gran2 + (size_t)(s > 0 ? s - 1 : 0) * (size_t)a.granStride;
-        // this lane's codes of column c: cw + (c - 1) TR / 2
-        unsigned char* const cw = a.codes + (size_t)t * (size_t)a.stripBytes + lane * (KR / 2);
-
-        int yo[KR], Hp[KR], E[KR];  // the rows' letters, 4 H (tag 0), 4 E (tag 0)
-#pragma unroll
-        for (int k = 0; k < KR; ++k)
-        {
-            yo[k] = a.seqY[min(i0 + 1 + k, a.iEnd)];
-            Hp[k] = 0;  // the free column 0: H = 0, no gap runs along it
-            E[k] = kNegQ;
-        }
-        int hdiag = 0;  // H(i0, 0)
-        int fLast = kNegQ | (int)kDbTraceF;
-        // the letter and the row above of the next step, loaded one step ahead
-        int letNext = (1 - lane >= 1 && 1 - lane <= J) ? x[1 - lane] : 0;
-        int2 aboveNext = make_int2(0, kNegQ | (int)kDbTraceF);
-        if (ck && J >= 1) aboveNext = checkpoint<AFFINE>(gh, gf, 1, iT, go, ge);
-
-        for (int step = 1; step <= W + 63; ++step)
-        {
-            const int c = step - lane;
-            const int let = letNext;
-            int2 above = aboveNext;
-            if (c + 1 >= 1 && c + 1 <= J)
-            {
-                letNext = x[c + 1];
-                if (ck) aboveNext = checkpoint<AFFINE>(gh, gf, c + 1, iT, go, ge);
-            }
-            if (s == 0)
-            {
-                above.x = 0;  // the free row: H = 0, no gap runs along it
-                above.y = kNegQ | (int)kDbTraceF;
-            }
-            const int hu0 = from_lane_above(above.x, Hp[KR - 1]);
-            const int fu0 = AFFINE ? from_lane_above(above.y, fLast) : 0;
-            if (c >= 1 && c <= J)
-            {
-                const int* const trow = tab + let * ssz;
-                int hup = hu0, fup = fu0, hdg = hdiag;
-                unsigned acc[NW];
-#pragma unroll
-                for (int w = 0; w < NW; ++w) acc[w] = 0u;
-#pragma unroll
-                for (int k = 0; k < KR; ++k)
-                {
-                    const int hp = Hp[k];
-                    const int d = hdg + trow[yo[k]];  // tag 2
-                    int e, f, h;
-                    unsigned nib;
-                    if (AFFINE)
-                    {
-                        const int eq = max(E[k] + ge4, hp + (go4 + 1));  // bit 0: opened
-                        const int fq = max(fup + ge4, hup + (go4 + 2));  // bit 1: opened
-                        e = eq & ~3;                                     // tag 0
-                        f = (fq & ~3) | (int)kDbTraceF;                  // tag 1
-                        nib = ((unsigned)eq & 1u) | ((unsigned)fq & 2u);
-                        E[k] = e;
-                        fup = f;
-                    }
-                    else
-                    {
-                        e = hp + go4;
-                        f = hup + (go4 + (int)kDbTraceF);
-                        nib = 0u;
-                    }
-                    h = max(max(d, e), f);
-                    nib = (nib << 2) | ((unsigned)h & 3u);
-                    acc[k / 8] |= nib << (4 * (k % 8));
-                    h &= ~3;
-                    hdg = hp;
-                    Hp[k] = h;
-                    hup = h;
-                }
-                fLast = fup;
-                hdiag = hu0;
-                // "opened" to "extended"
-                const unsigned flip = AFFINE ? 0xccccccccu : 0u;
-                CodesN<NW> out;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) out.w[w] = acc[w] ^ flip;
-                *reinterpret_cast<CodesN<NW>*>(cw + (size_t)(c - 1) * (TR / 2)) = out;
-            }
-        }
+        const size_t grow = (size_t)(s > 0 ? s - 1 : 0) * (size_t)a.granStride;
+        StripTask task;
+        task.s = s;
+        task.seqY = a.seqY;
+        task.x = a.seqX;
+        task.clampRow = a.iEnd;
+        task.lastRow = a.iEnd;
+        task.W = a.J;
+        task.jW = 0;
+        task.gh = a.gran + grow;
+        task.gf = a.gran2 + grow;
+        task.cw = a.codes + (size_t)t * (size_t)a.stripBytes;
+        GSA_PAIR_STRIP_FILL((kOverlap), AFFINE, KR, task, tab, ssz, a.go, a.ge);
     }
 }
 
-// One lane.  State kWalkH, or kDbTraceF / kDbTraceE inside a gap; every trip of the loop emits one
-// move or ends the walk, so the walk takes at most i_end + j_end trips over all chunks.
 __global__ __launch_bounds__(64) void nw_overlap_walk_kernel(OverlapWalkArgs a)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const OverlapWalkRec r = *a.rec;
-    const int* const x = a.seqX;
-    const int* const y = a.seqY;
-    unsigned char* const mv = a.moves;
-    const int ks = a.krShift, KR = 1 << ks, TRm = (64 << ks) - 1;
-    int i = r.i, j = r.j, n = r.n;
-    unsigned state = r.state;
-    bool done = r.done != 0;
-    while (!done && !(a.iStop > 0 && i == a.iStop && j > 0))
-    {
-        if (i == 0 || j == 0)
-        {
-            done = true;  // on a free border: the overhang stays out of the alignment
-            break;
-        }
-        const int rr = (i - 1) & TRm, t = ((i - 1) >> (6 + ks)) - a.tLo;
-        const int l = rr >> ks, k = rr & (KR - 1);
-        const size_t at = (size_t)t * (size_t)a.stripBytes + (size_t)(j - 1) * (size_t)(32 << ks) +
-                          (size_t)(l * (KR / 2) + (k >> 3) * 4);
-        const unsigned code = (*reinterpret_cast<const unsigned*>(a.codes + at) >> (4 * (k & 7))) & 15u;
-        const unsigned src = code & 3u;
-        const unsigned eff = state == kWalkH ? src : state;
-        const bool diag = eff == kDbTraceDiag, up = eff == kDbTraceF, left_ = eff == kDbTraceE;
-        const bool ext = (up && (code & kDbTraceFExt)) || (left_ && (code & kDbTraceEExt));
-        const bool same = y[i] == x[j];
-        mv[n] = diag ? (same ? '=' : 'X') : (up ? 'I' : 'D');
-        n += 1;
-        i -= (diag || up) ? 1 : 0;
-        j -= (diag || left_) ? 1 : 0;
-        state = ext ? eff : kWalkH;
-    }
-    if (i == 0 || j == 0) done = true;
-    OverlapWalkRec o;
-    o.i = i;
-    o.j = j;
-    o.state = state;
-    o.n = n;
-    o.done = done ? 1 : 0;
-    o.pad0 = o.pad1 = o.pad2 = 0;
-    *a.rec = o;
-}
-
-template <bool AFFINE, int KR>
-hipError_t fill_grid(int nstrips, int* grid)
-{
-    auto kern = nw_overlap_fill_kernel<AFFINE, KR>;
-    int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0);
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) *grid = std::max(1, std::min(nstrips, std::min(std::max(1, per_cu), kFillWgsPerCu) * std::max(1, cus)));
-    return e;
-}
-
-template <bool AFFINE, int KR>
-hipError_t launch_fill(const OverlapFillArgs& a, int grid, hipStream_t st)
-{
-    auto kern = nw_overlap_fill_kernel<AFFINE, KR>;
-    hipError_t e = record_foot((const void*)kern, 0, 64, grid);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, st, a);
-    return hipGetLastError();
+    const WalkTask w = {a.seqY, a.seqX, a.codes, a.stripBytes, a.krShift, a.tLo, a.iStop, 0, a.moves};
+    GSA_OVERLAP_WALK(w, *a.rec);
 }
 
 template <int KR>
 hipError_t launch_fill_kr(const OverlapFillArgs& a, int grid, hipStream_t st)
 {
-    return a.go != a.ge ? launch_fill<true, KR>(a, grid, st) : launch_fill<false, KR>(a, grid, st);
+    return a.go != a.ge ? launch_fill_for(nw_overlap_fill_kernel<true, KR>, a, grid, st)
+                        : launch_fill_for(nw_overlap_fill_kernel<false, KR>, a, grid, st);
 }
 
 }  // namespace
@@ -252,8 +69,11 @@ hipError_t launch_fill_kr(const OverlapFillArgs& a, int grid, hipStream_t st)
 hipError_t overlap_fill_grid(bool affine, int KR, int nstrips, int* grid)
 {
     if (KR != 8 && KR != 16) return hipErrorInvalidValue;
-    if (KR == 8) return affine ? fill_grid<true, 8>(nstrips, grid) : fill_grid<false, 8>(nstrips, grid);
-    return affine ? fill_grid<true, 16>(nstrips, grid) : fill_grid<false, 16>(nstrips, grid);
+    if (KR == 8)
+        return affine ? fill_grid_for(nw_overlap_fill_kernel<true, 8>, nstrips, 0, grid)
+                      : fill_grid_for(nw_overlap_fill_kernel<false, 8>, nstrips, 0, grid);
+    return affine ? fill_grid_for(nw_overlap_fill_kernel<true, 16>, nstrips, 0, grid)
+                  : fill_grid_for(nw_overlap_fill_kernel<false, 16>, nstrips, 0, grid);
 }
 
 hipError_t launch_overlap_trace(const OverlapFillArgs& f, const OverlapWalkArgs& w, int KR, int grid, hipEvent_t* ev, hipStream_t st)
