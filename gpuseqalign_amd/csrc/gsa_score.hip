@@ -1090,6 +1090,55 @@ std::string fold_cigar(const unsigned char* mv, int64_t n)
     return s;
 }
 
+// The CIGARs of the n results with status 0 into the caller's buffer, back to back in order, each with
+// its terminator; one that does not fit gets status 2.  A string's offset does not depend on the
+// buffer's size.  Returns the bytes all of them take (*cigar_need).
+int64_t pack_cigars(gsa_align_db_result* res, const std::string* cig, int64_t n, char* cigar, int64_t cigar_cap)
+{
+    int64_t at = 0;
+    for (int64_t k = 0; k < n; ++k)
+    {
+        gsa_align_db_result& r = res[k];
+        if (r.status != 0) continue;
+        const int64_t len = (int64_t)cig[k].size();
+        if (at + len + 1 <= cigar_cap)
+        {
+            std::memcpy(cigar + at, cig[k].c_str(), (size_t)len + 1);
+            r.cigar_off = at;
+            r.cigar_len = len;
+        }
+        else
+            r.status = 2;
+        at += len + 1;
+    }
+    return at;
+}
+
+// The three events a fill launch and a walk launch are timed with (the launchers record them), made on
+// first use.
+int ensure_trace_events(gsa_ctx* ctx)
+{
+    for (hipEvent_t& ev : ctx->adbev)
+    {
+        const hipError_t e = ev ? hipSuccess : hipEventCreate(&ev);
+        if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+    }
+    return GSA_SUCCESS;
+}
+
+// Adds the times of the fill and of the walk those events were last recorded around.
+void add_trace_ms(const gsa_ctx* ctx, float* fill_ms, float* walk_ms)
+{
+    float m0 = 0.f, m1 = 0.f;
+    (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
+    (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
+    *fill_ms += m0;
+    *walk_ms += m1;
+}
+
+// log2 of the rows a lane's codes hold (KR = 8 or 16): the walks' krShift
+int kr_shift(int KR) { return KR == 8 ? 3 : 4; }
+
 // gsa_align_db_dev: hits with an empty side on the host; the hits the trace kernels take, longest
 // first, in chunks whose move codes fit scratch_limit, a fill and a walk launch per chunk and one copy
 // of the results and move bytes back (nw_lanes_trace.hip); the others (status 1) through
@@ -1215,8 +1264,7 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
             const size_t bb = (size_t)maxGrid * gsa::kDbLanesWaves * gsa::kDbLanesSubj * (size_t)(cmax + 1) * sizeof(int2);
             if ((s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bb, 4096)) != GSA_SUCCESS) return s;
         }
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        if (const int es = ensure_trace_events(ctx); es != GSA_SUCCESS) return es;
         char* const meta = ctx->buf[kBufAdbMeta].as<char>();
         unsigned char* const adbres = ctx->buf[kBufAdbRes].as<unsigned char>();
         std::vector<char> hmeta(lenAt + maxN * 4), hres(resBytes);
@@ -1273,11 +1321,7 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
             if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)mb, hipMemcpyDeviceToHost, st)) != hipSuccess ||
                 (e = hipStreamSynchronize(st)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            float m0 = 0.f, m1 = 0.f;
-            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-            fill_ms += m0;
-            walk_ms += m1;
+            add_trace_ms(ctx, &fill_ms, &walk_ms);
             const gsa::DbTraceOut* const ho = (const gsa::DbTraceOut*)hres.data();
             for (size_t k = 0; k < n; ++k)
             {
@@ -1325,25 +1369,8 @@ int align_db_impl(gsa_ctx* ctx, const int32_t* query, int32_t adjq, const int32_
         }
         inf.unsupported = (int32_t)other.size();
     }
-    // the strings back to back in hit order; a hit's offset does not depend on the buffer's size
-    int64_t at = 0;
-    for (int h = 0; h < nhits; ++h)
-    {
-        gsa_align_db_result& r = out[h];
-        const int64_t len = (int64_t)cig[(size_t)h].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)h].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
-    }
+    // the strings back to back in hit order
+    const int64_t at = pack_cigars(out, cig.data(), nhits, cigar, cigar_cap);
     if (cigar_need) *cigar_need = at;
     inf.fill_ms = fill_ms;
     inf.walk_ms = walk_ms;
@@ -1879,8 +1906,7 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             (s = reserve_hard(ctx, ctx->buf[kBufAdbCodes], (size_t)maxCodes, 4096)) != GSA_SUCCESS)
             return s;
         if (bndBytes && (s = reserve_hard(ctx, ctx->buf[kBufDbbnd], bndBytes, 4096)) != GSA_SUCCESS) return s;
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        if (const int es = ensure_trace_events(ctx); es != GSA_SUCCESS) return es;
         char* const meta = ctx->buf[kBufAdbMeta].as<char>();
         unsigned char* const adbres = ctx->buf[kBufAdbRes].as<unsigned char>();
         if ((e = hipMemsetAsync(meta, 0, 64, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
@@ -1966,11 +1992,7 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
             if ((e = hipMemcpyAsync(hres.data(), adbres, movAt + (size_t)ch.moveBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
                 (e = hipStreamSynchronize(st)) != hipSuccess)
                 return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            float m0 = 0.f, m1 = 0.f;
-            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-            fill_ms += m0;
-            walk_ms += m1;
+            add_trace_ms(ctx, &fill_ms, &walk_ms);
             const gsa::DbTraceOut* const ho = (const gsa::DbTraceOut*)hres.data();
             for (size_t k = 0; k < n; ++k)
             {
@@ -2025,25 +2047,8 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
         }
         inf.unsupported = (int32_t)other.size();
     }
-    // the strings back to back in hit order; a hit's offset does not depend on the buffer's size
-    int64_t at = 0;
-    for (int h = 0; h < nhits; ++h)
-    {
-        gsa_align_db_result& r = out[h];
-        const int64_t len = (int64_t)cig[(size_t)h].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)h].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
-    }
+    // the strings back to back in hit order
+    const int64_t at = pack_cigars(out, cig.data(), nhits, cigar, cigar_cap);
     if (cigar_need) *cigar_need = at;
     inf.fill_ms = fill_ms;
     inf.walk_ms = walk_ms;
@@ -2052,12 +2057,166 @@ int align_db_multi_impl(gsa_ctx* ctx, const int32_t* queries, const int64_t* q_o
     return GSA_SUCCESS;
 }
 
+// ---- One long pair traced from its score launch's checkpoint rows: the chunk loop ----
+//
+// trace_pair is the host loop of gsa_align_pair_dev, gsa_align_pair_semi_dev and
+// gsa_align_pair_overlap_dev.  The score launch left the bottom row of each of its strips in kBufGran.
+// The walk starts on (iEnd, jEnd) in state H; its record lives at kBufPairMeta + 64, the fill's task
+// counter at kBufPairMeta + 0, the moves in kBufPairMoves (at most iEnd + jEnd - jW of them).  The caller
+// planned the first chunk (only it knows what a limit below one strip means for its mode).  Per chunk:
+// kBufPairCodes for its codes, the counter zeroed, one fill and one walk launch (the mode's launcher),
+// the record copied back; a finished walk ends the loop, any other must stand on the chunk's upper
+// boundary (the mode's go-on test), and the next chunk is semi_plan_chunk's for the columns
+// jW + 1 ... rec.j.  At the end the moves are copied back and folded into the CIGAR.
+//
+// A mode is a struct of types and static functions: FillArgs, WalkArgs and WalkRec of its trace unit;
+// mode_args, which sets the fields of the two argument structs only that unit has; launch (its
+// *_fill_grid and launch_*_trace); rec_ok, go_on and end_ok, its checks of a returned record.
+
+// What the loop needs of the call and of its score launch.
+struct PairTrace
+{
+    const int32_t *seqY, *seqX, *subst;
+    int32_t substsz, gapo, gape, local;
+    int64_t R, C;        // letters of seqY and of seqX
+    int64_t iEnd, jEnd;  // the cell the walk starts on
+    int64_t jW;          // codes are kept for the columns jW + 1 ... jEnd; 0 in the modes without a window
+    int KR;              // rows of a lane in the codes; a strip has 64 KR rows
+    int64_t tickets;     // strips of the score launch: its second array lies that many rows behind the first
+    int64_t limit;       // bytes of codes held at once
+};
+
+template <class Mode, class Info>
+int trace_pair(gsa_ctx* ctx, const PairTrace& t, gsa::PairChunk ch, Info* inf, gsa_align_db_result* r, std::string* cig,
+               hipStream_t st)
+{
+    using Rec = typename Mode::WalkRec;
+    const int64_t TR = 64 * (int64_t)t.KR;
+    const int64_t maxMoves = t.iEnd + t.jEnd - t.jW;
+    int s;
+    hipError_t e;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
+        (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)maxMoves, 4096)) != GSA_SUCCESS ||
+        (s = ensure_trace_events(ctx)) != GSA_SUCCESS)
+        return s;
+    char* const meta = ctx->buf[kBufPairMeta].as<char>();
+    Rec* const drec = (Rec*)(meta + 64);
+    const size_t stride = (size_t)gsa::gran_stride((int)t.C);
+    Rec rec;
+    std::memset(&rec, 0, sizeof(rec));
+    rec.i = (int)t.iEnd;
+    rec.j = (int)t.jEnd;
+    rec.state = 4u;
+    if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    for (;;)
+    {
+        const int nstrips = (int)(ch.tHi - ch.tLo + 1);
+        if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
+        if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        typename Mode::FillArgs f;
+        std::memset(&f, 0, sizeof(f));
+        f.seqY = t.seqY;
+        f.seqX = t.seqX;
+        f.subst = t.subst;
+        f.substsz = t.substsz;
+        f.go = t.gapo;
+        f.ge = t.gape;
+        f.J = (int)(t.jW + ch.J);  // the chunk's last column
+        f.tLo = (int)ch.tLo;
+        f.nstrips = nstrips;
+        f.gran = ctx->buf[kBufGran].as<unsigned long long>();
+        f.gran2 = f.gran + (size_t)t.tickets * stride;
+        f.granStride = (long long)stride;
+        f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
+        f.stripBytes = ch.stripBytes;
+        f.counter = (unsigned*)meta;
+        typename Mode::WalkArgs w;
+        std::memset(&w, 0, sizeof(w));
+        w.seqY = t.seqY;
+        w.seqX = t.seqX;
+        w.codes = f.codes;
+        w.stripBytes = ch.stripBytes;
+        w.krShift = kr_shift(t.KR);
+        w.tLo = (int)ch.tLo;
+        w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
+        w.rec = drec;
+        w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
+        Mode::mode_args(t, f, w);
+        if ((e = Mode::launch(t, f, w, ctx->adbev, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        add_trace_ms(ctx, &inf->fill_ms, &inf->walk_ms);
+        inf->chunks += 1;
+        inf->strips_filled += nstrips;
+        inf->code_bytes = std::max<int64_t>(inf->code_bytes, ch.codeBytes);
+        // moves written past their buffer, or a record the mode does not take
+        if (rec.n < 0 || rec.n > maxMoves || !Mode::rec_ok(t, ch, rec)) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+        if (rec.done) break;
+        // on the chunk's upper boundary: the next chunk, for the columns up to here
+        if (!Mode::go_on(t, TR, ch, rec) || !gsa::semi_plan_chunk(TR, ch.tLo - 1, rec.j, t.jW, t.limit, &ch))
+            return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+    }
+    if (!Mode::end_ok(rec)) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+    std::vector<unsigned char> mv((size_t)rec.n + 1);
+    if (rec.n > 0 &&
+        ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+         (e = hipStreamSynchronize(st)) != hipSuccess))
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    *cig = fold_cigar(mv.data(), rec.n);
+    r->i_start = rec.i;
+    r->j_start = rec.j;
+    r->status = 0;
+    return GSA_SUCCESS;
+}
+
+// The single-pair calls' shared end: the CIGAR into the caller's buffer (status 2 when it does not
+// fit), the bytes it needs, the info and the kernel time.
+template <class Info>
+int finish_pair(gsa_align_db_result r, const std::string& cig, const Info& inf, gsa_align_db_result* out, char* cigar,
+                int64_t cigar_cap, int64_t* cigar_need, Info* info, float* kernel_ms)
+{
+    const int64_t need = pack_cigars(&r, &cig, 1, cigar, cigar_cap);
+    if (cigar_need) *cigar_need = need;
+    *out = r;
+    if (info) *info = inf;
+    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    return GSA_SUCCESS;
+}
+
+// gsa_align_pair_dev's unit (nw_pair_trace.hip): rows 1 ... iEnd of a pair of R rows, global or local.  A
+// local path may end anywhere, so a finished record is taken as it stands.
+struct GlobalTrace
+{
+    using FillArgs = gsa::PairFillArgs;
+    using WalkArgs = gsa::PairWalkArgs;
+    using WalkRec = gsa::PairWalkRec;
+    static void mode_args(const PairTrace& t, FillArgs& f, WalkArgs& w)
+    {
+        f.local = w.local = t.local ? 1 : 0;
+        f.R = (int)t.R;
+        f.iEnd = (int)t.iEnd;
+    }
+    static hipError_t launch(const PairTrace& t, const FillArgs& f, const WalkArgs& w, hipEvent_t* ev, hipStream_t st)
+    {
+        int grid = 1;
+        const hipError_t e = gsa::pair_fill_grid(f.local, t.gapo != t.gape, t.KR, f.nstrips, &grid);
+        return e != hipSuccess ? e : gsa::launch_pair_trace(f, w, t.KR, grid, ev, st);
+    }
+    static bool rec_ok(const PairTrace&, const gsa::PairChunk&, const WalkRec&) { return true; }
+    static bool go_on(const PairTrace&, int64_t TR, const gsa::PairChunk& ch, const WalkRec& r)
+    {
+        return ch.tLo >= 1 && r.i == gsa::pair_chunk_stop_row(TR, ch) && r.j >= 1 && r.j <= ch.J;
+    }
+    static bool end_ok(const WalkRec&) { return true; }
+};
+
 // gsa_align_pair_dev: the score from the K-rows score kernel in one direction (score_ag_strip with a
-// route), whose checkpoint rows stay in kBufGran; then, bottom-up, chunks of strips whose move codes
-// fit scratch_limit (nw_pair_trace_plan.h), a fill and a walk launch per chunk and one small copy of
-// the walk's record back (nw_pair_trace.hip); at the end the move bytes, folded into the CIGAR.  A
-// pair the K-rows kernel or the 4 v + tag form does not take, or whose single strip exceeds the
-// limit, gets its score and end cell and status 1.  gsa_last_launch's record is left as it was.
+// route), whose checkpoint rows stay in kBufGran; then trace_pair from the end cell.  A pair the K-rows
+// kernel or the 4 v + tag form does not take, or whose single strip exceeds the limit, gets its score
+// and end cell and status 1.  gsa_last_launch's record is left as it was.
 int align_pair_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                     const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int32_t local,
                     int64_t scratch_limit, gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -2144,120 +2303,261 @@ int align_pair_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const in
                 gsa::PairChunk ch;
                 if (iEnd >= 1 && jEnd >= 1 && gsa::pair_plan_chunk(TR, strips - 1, jEnd, limit, &ch))
                 {
-                    if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
-                        (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(iEnd + jEnd), 4096)) != GSA_SUCCESS)
-                        return s;
-                    for (hipEvent_t& ev : ctx->adbev)
-                        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-                    char* const meta = ctx->buf[kBufPairMeta].as<char>();
-                    gsa::PairWalkRec* const drec = (gsa::PairWalkRec*)(meta + 64);
-                    const size_t stride = (size_t)gsa::gran_stride((int)C);
-                    gsa::PairWalkRec rec;
-                    std::memset(&rec, 0, sizeof(rec));
-                    rec.i = (int)iEnd;
-                    rec.j = (int)jEnd;
-                    rec.state = 4u;
-                    if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
-                        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                    for (;;)
-                    {
-                        const int nstrips = (int)(ch.tHi - ch.tLo + 1);
-                        if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
-                        if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                        gsa::PairFillArgs f;
-                        std::memset(&f, 0, sizeof(f));
-                        f.seqY = seqY;
-                        f.seqX = seqX;
-                        f.subst = subst;
-                        f.substsz = substsz;
-                        f.go = gapo;
-                        f.ge = gape;
-                        f.local = local ? 1 : 0;
-                        f.R = (int)R;
-                        f.iEnd = (int)iEnd;
-                        f.J = (int)ch.J;
-                        f.tLo = (int)ch.tLo;
-                        f.nstrips = nstrips;
-                        f.gran = ctx->buf[kBufGran].as<unsigned long long>();
-                        f.gran2 = f.gran + (size_t)route.tickets * stride;
-                        f.granStride = (long long)stride;
-                        f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
-                        f.stripBytes = ch.stripBytes;
-                        f.counter = (unsigned*)meta;
-                        gsa::PairWalkArgs w;
-                        std::memset(&w, 0, sizeof(w));
-                        w.seqY = seqY;
-                        w.seqX = seqX;
-                        w.codes = f.codes;
-                        w.stripBytes = ch.stripBytes;
-                        w.krShift = KR == 8 ? 3 : 4;
-                        w.tLo = (int)ch.tLo;
-                        w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
-                        w.local = f.local;
-                        w.rec = drec;
-                        w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
-                        int grid = 1;
-                        if ((e = gsa::pair_fill_grid(f.local, gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
-                            (e = gsa::launch_pair_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
-                            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                        note_launch(ctx);
-                        if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                            (e = hipStreamSynchronize(st)) != hipSuccess)
-                            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                        float m0 = 0.f, m1 = 0.f;
-                        (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-                        (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-                        inf.fill_ms += m0;
-                        inf.walk_ms += m1;
-                        inf.chunks += 1;
-                        inf.strips_filled += nstrips;
-                        inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
-                        if (rec.n < 0 || rec.n > iEnd + jEnd) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                        if (rec.done) break;
-                        // on the chunk's upper boundary: the next chunk, for the columns up to here
-                        if (ch.tLo < 1 || rec.i != w.iStop || rec.j < 1 || rec.j > ch.J ||
-                            !gsa::pair_plan_chunk(TR, ch.tLo - 1, rec.j, limit, &ch))
-                            return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                    }
-                    std::vector<unsigned char> mv((size_t)rec.n + 1);
-                    if (rec.n > 0 &&
-                        ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) !=
-                             hipSuccess ||
-                         (e = hipStreamSynchronize(st)) != hipSuccess))
-                        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                    cig = fold_cigar(mv.data(), rec.n);
-                    r.i_start = rec.i;
-                    r.j_start = rec.j;
-                    r.status = 0;
+                    const PairTrace t {seqY, seqX, subst, substsz, gapo, gape, local, R, C, iEnd, jEnd, 0, KR, route.tickets, limit};
+                    if ((s = trace_pair<GlobalTrace>(ctx, t, ch, &inf, &r, &cig, st)) != GSA_SUCCESS) return s;
                 }
             }
         }
     }
-    const int64_t len = (int64_t)cig.size();
-    if (r.status == 0)
+    return finish_pair(r, cig, inf, out, cigar, cigar_cap, cigar_need, info, kernel_ms);
+}
+
+// ---- A batch of long pairs traced from their score launch's checkpoint rows: the round loop (2.2j) ----
+//
+// trace_batch is the host loop of gsa_align_batch_dev, gsa_align_batch_semi_dev and
+// gsa_align_batch_overlap_dev, over the pairs the caller chose to trace.  The batched score launch left
+// every pair's checkpoint rows in kBufGran, at its own granOff.  Every walk starts on its pair's
+// (iEnd, jEnd) in state H; the records live in kBufPairBatchRec, all moves in kBufPairMoves (pair b's at
+// the sum of its predecessors' iEnd + jEnd - jW).  Per round (nw_pair_trace_batch_plan.h):
+// kBufPairCodes for the round's codes; a descriptor and a walk per chunk and a task per strip, the
+// tasks by width descending (the longest chains first); one upload into kBufPairBatchTab of the task
+// counter (64 bytes, zero), the tasks, the descriptors and the walks; one fill and one walk launch (the
+// mode's launcher); the records copied back; each checked and its pair moved on by the mode's advance
+// rule.  At the end one copy of all moves, folded into the CIGARs.
+//
+// A mode is a struct of types and static functions: Desc, Walk, FillArgs, WalkArgs and WalkRec of its
+// trace unit; base, the PairBatchDesc inside a Desc; window, which sets the fields only that unit has;
+// launch (its *_batch_fill_grid and launch_*_batch_trace); rec_ok and advance.
+
+// What the loop needs of the call and of its score launch.
+struct BatchTrace
+{
+    const gsa_pair_dev* pairs;
+    const int32_t* subst;
+    int32_t substsz, gapo, gape, local, max_workgroups;
+    int KR;               // rows of a lane in the codes; a strip has 64 KR rows
+    long long granTotal;  // words of the score launch's first array: the second lies that far behind
+    int64_t limit;        // bytes of codes held at once
+};
+
+// A pair the loop traces.
+struct BatchTracePair
+{
+    int p;               // index into the call's pairs
+    int64_t iEnd, jEnd;  // the cell its walk starts on
+    int64_t jW;          // its column window; 0 in the modes without one
+    long long granOff;   // its first checkpoint row within kBufGran, in words
+};
+
+template <class Mode, class Info>
+int trace_batch(gsa_ctx* ctx, const BatchTrace& t, const std::vector<BatchTracePair>& bp, Info* inf, gsa_align_db_result* res,
+                std::string* cig, hipStream_t st)
+{
+    using Rec = typename Mode::WalkRec;
+    using Desc = typename Mode::Desc;
+    using Walk = typename Mode::Walk;
+    const int64_t TR = 64 * (int64_t)t.KR;
+    const size_t nb = bp.size();
+    inf->batch_pairs = (int32_t)nb;
+    std::vector<int64_t> movOff(nb);
+    int64_t movTotal = 0;
+    for (size_t b = 0; b < nb; ++b)
     {
-        if (len + 1 <= cigar_cap)
-        {
-            std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
-            r.cigar_len = len;
-        }
-        else
-            r.status = 2;
-        if (cigar_need) *cigar_need = len + 1;
+        movOff[b] = movTotal;
+        movTotal += bp[b].iEnd + bp[b].jEnd - bp[b].jW;
     }
-    *out = r;
-    if (info) *info = inf;
-    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
+    int s;
+    hipError_t e;
+    if ((s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
+        (s = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(Rec), 4096)) != GSA_SUCCESS ||
+        (s = ensure_trace_events(ctx)) != GSA_SUCCESS)
+        return s;
+    Rec* const drec = ctx->buf[kBufPairBatchRec].as<Rec>();
+    unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
+    const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
+    std::vector<Rec> rec(nb);
+    std::memset(rec.data(), 0, nb * sizeof(Rec));
+    std::vector<gsa::BatchPairState> state(nb);
+    for (size_t b = 0; b < nb; ++b)
+    {
+        rec[b].i = (int)bp[b].iEnd;
+        rec[b].j = (int)bp[b].jEnd;
+        rec[b].state = 4u;
+        state[b].tHi = gsa::pair_strips(TR, bp[b].iEnd) - 1;
+        state[b].J = bp[b].jEnd;
+        state[b].jW = bp[b].jW;
+        inf->strips += (int32_t)(state[b].tHi + 1);
+    }
+    if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(Rec), hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    std::vector<gsa::BatchChunk> chunks;
+    std::vector<gsa::PairBatchTask> tasks;
+    std::vector<Desc> descs;
+    std::vector<Walk> walks;
+    std::vector<char> blob;
+    for (;;)
+    {
+        const long long used = gsa::batch_plan_round(TR, t.limit, state, &chunks);
+        if (chunks.empty())
+        {
+            for (const gsa::BatchPairState& S : state)
+                if (S.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
+            break;
+        }
+        if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096)) != GSA_SUCCESS) return s;
+        unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
+        tasks.clear();
+        descs.clear();
+        walks.clear();
+        for (size_t c = 0; c < chunks.size(); ++c)
+        {
+            const gsa::BatchChunk& ch = chunks[c];
+            const BatchTracePair& B = bp[(size_t)ch.pair];
+            const gsa_pair_dev& P = t.pairs[B.p];
+            Desc d;
+            std::memset(&d, 0, sizeof(d));
+            gsa::PairBatchDesc& pd = Mode::base(d);
+            pd.seqY = P.seqY;
+            pd.seqX = P.seqX;
+            pd.R = P.adjrows - 1;
+            pd.iEnd = (int)B.iEnd;
+            pd.J = (int)(B.jW + ch.c.J);  // the chunk's last column
+            pd.granBase = B.granOff;
+            pd.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
+            pd.stripBytes = ch.c.stripBytes;
+            for (long long strip = ch.c.tLo; strip <= ch.c.tHi; ++strip)
+            {
+                gsa::PairBatchTask k;
+                k.pair = (int)c;
+                k.strip = (int)strip;
+                k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, strip);
+                tasks.push_back(k);
+            }
+            Walk w;
+            std::memset(&w, 0, sizeof(w));
+            w.seqY = P.seqY;
+            w.seqX = P.seqX;
+            w.codes = dcodes + ch.codeOff;
+            w.stripBytes = ch.c.stripBytes;
+            w.tLo = (int)ch.c.tLo;
+            w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
+            w.rec = ch.pair;
+            w.moves = dmoves + movOff[(size_t)ch.pair];
+            Mode::window(B, d, w);
+            descs.push_back(d);
+            walks.push_back(w);
+        }
+        // the longest chains first
+        std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
+            return chunks[(size_t)a.pair].c.J > chunks[(size_t)b.pair].c.J;
+        });
+        // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
+        const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
+                     oWalk = oDesc + descs.size() * sizeof(Desc), tabBytes = oWalk + walks.size() * sizeof(Walk);
+        if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
+        char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
+        blob.assign(tabBytes, 0);
+        std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
+        std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(Desc));
+        std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(Walk));
+        if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+        typename Mode::FillArgs f;
+        std::memset(&f, 0, sizeof(f));
+        f.pairs = (const Desc*)(dtab + oDesc);
+        f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
+        f.ntasks = (int)tasks.size();
+        f.subst = t.subst;
+        f.substsz = t.substsz;
+        f.go = t.gapo;
+        f.ge = t.gape;
+        f.gran = dgran;
+        f.gran2 = dgran + t.granTotal;
+        f.codes = dcodes;
+        f.counter = (unsigned*)dtab;
+        typename Mode::WalkArgs w;
+        std::memset(&w, 0, sizeof(w));
+        w.walks = (const Walk*)(dtab + oWalk);
+        w.nwalks = (int)walks.size();
+        w.krShift = kr_shift(t.KR);
+        w.recs = drec;
+        const int walkGrid = t.max_workgroups > 0 ? std::min(w.nwalks, (int)t.max_workgroups) : w.nwalks;
+        if ((e = Mode::launch(t, f, w, walkGrid, ctx->adbev, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        note_launch(ctx);
+        if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(Rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = hipStreamSynchronize(st)) != hipSuccess)
+            return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
+        add_trace_ms(ctx, &inf->fill_ms, &inf->walk_ms);
+        inf->rounds += 1;
+        inf->strips_filled += (int32_t)tasks.size();
+        inf->code_bytes = std::max<int64_t>(inf->code_bytes, used);
+        // every record that came back: in range, and finished or on its chunk's upper boundary as its mode has it
+        for (const gsa::BatchChunk& ch : chunks)
+        {
+            const BatchTracePair& B = bp[(size_t)ch.pair];
+            const Rec& r = rec[(size_t)ch.pair];
+            if (r.n < 0 || r.n > B.iEnd + B.jEnd - B.jW || r.i < 0 || r.i > B.iEnd || r.j < 0 || r.j > B.jW + ch.c.J ||
+                !Mode::rec_ok(r) || !Mode::advance(TR, ch.c, r.i, r.j, r.done != 0, &state[(size_t)ch.pair]))
+                return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
+        }
+    }
+    std::vector<unsigned char> mv((size_t)movTotal + 1);
+    if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
+    for (size_t b = 0; b < nb; ++b)
+    {
+        gsa_align_db_result& r = res[(size_t)bp[b].p];
+        cig[(size_t)bp[b].p] = fold_cigar(mv.data() + movOff[b], rec[b].n);
+        r.i_start = rec[b].i;
+        r.j_start = rec[b].j;
+        r.status = 0;
+    }
     return GSA_SUCCESS;
 }
 
+// The batch calls' shared end: the strings back to back in pair order, the results, the bytes the
+// strings need and the info.
+template <class Info>
+void finish_batch(std::vector<gsa_align_db_result>& res, const std::vector<std::string>& cig, const Info& inf,
+                  gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need, Info* info)
+{
+    const int64_t need = pack_cigars(res.data(), cig.data(), (int64_t)res.size(), cigar, cigar_cap);
+    std::copy(res.begin(), res.end(), out);
+    if (cigar_need) *cigar_need = need;
+    if (info) *info = inf;
+}
+
+// gsa_align_batch_dev's unit (nw_pair_trace_batch.hip)
+struct GlobalBatchTrace
+{
+    using Desc = gsa::PairBatchDesc;
+    using Walk = gsa::PairBatchWalk;
+    using FillArgs = gsa::PairBatchFillArgs;
+    using WalkArgs = gsa::PairBatchWalkArgs;
+    using WalkRec = gsa::PairWalkRec;
+    static gsa::PairBatchDesc& base(Desc& d) { return d; }
+    static void window(const BatchTracePair&, Desc&, Walk&) {}
+    static hipError_t launch(const BatchTrace& t, const FillArgs& f, WalkArgs w, int walkGrid, hipEvent_t* ev, hipStream_t st)
+    {
+        w.local = t.local ? 1 : 0;
+        int grid = 1;
+        const hipError_t e = gsa::pair_batch_fill_grid(w.local, t.gapo != t.gape, t.KR, f.ntasks, t.max_workgroups, &grid);
+        return e != hipSuccess ? e : gsa::launch_pair_batch_trace(f, w.local, w, t.KR, grid, walkGrid, ev, st);
+    }
+    static bool rec_ok(const WalkRec&) { return true; }
+    static bool advance(long long TR, const gsa::PairChunk& c, long long i, long long j, bool done, gsa::BatchPairState* s)
+    {
+        return gsa::pair_batch_advance(TR, c, i, j, done, s);
+    }
+};
+
 // gsa_align_batch_dev: the pairs' scores from score_batch_impl's launch (with a route), whose
-// checkpoint rows stay in kBufGran, every pair's at its own granOff; then rounds of one fill launch
-// over the strips of many pairs, one walk launch and one copy of the walks' records back
-// (nw_pair_trace_batch_plan.h, nw_pair_trace_batch.hip), while those rows are still there; at the end
-// the move bytes of all pairs in one copy, folded into the CIGARs.  The pairs that launch did not run
-// or flagged go through align_pair_impl afterwards, one by one: that call overwrites kBufGran and
-// reuses the kBufPair* slots.  gsa_last_launch's record is left as it was.
+// checkpoint rows stay in kBufGran, every pair's at its own granOff; then trace_batch over the pairs
+// that launch scored, while those rows are still there.  The pairs that launch did not run or flagged
+// go through align_pair_impl afterwards, one by one: that call overwrites kBufGran and reuses the
+// kBufPair* slots.  gsa_last_launch's record is left as it was.
 int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                      int32_t gapo, int32_t gape, int32_t local, int32_t max_workgroups, int64_t scratch_limit,
                      gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -2339,13 +2639,7 @@ int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
         const int KR = K * gsa::kSparseNS;
         const int64_t TR = 64 * (int64_t)KR;
         // the batch pairs: scored by the launch, a positive score, and one strip within the limit
-        struct Bp
-        {
-            int p, k;  // index into pairs, into sel
-            int64_t iEnd, jEnd, movOff;
-        };
-        std::vector<Bp> bp;
-        int64_t movTotal = 0;
+        std::vector<BatchTracePair> bp;
         for (size_t k = 0; k < sel.size(); ++k)
         {
             const int p = sel[k];
@@ -2367,177 +2661,13 @@ int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
                 continue;
             }
             if (r.i_end < 1 || r.j_end < 1 || gsa::pair_strip_bytes(TR, r.j_end) > limit) continue;
-            bp.push_back(Bp {p, (int)k, r.i_end, r.j_end, movTotal});
-            movTotal += r.i_end + r.j_end;
+            bp.push_back(BatchTracePair {p, r.i_end, r.j_end, 0, route.granOff[k]});
         }
         if (!bp.empty())
         {
-            const size_t nb = bp.size();
-            inf.batch_pairs = (int32_t)nb;
-            int sr;
-            if ((sr = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
-                (sr = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(gsa::PairWalkRec), 4096)) != GSA_SUCCESS)
-                return sr;
-            for (hipEvent_t& ev : ctx->adbev)
-                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-            gsa::PairWalkRec* const drec = ctx->buf[kBufPairBatchRec].as<gsa::PairWalkRec>();
-            unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
-            const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
-            std::vector<gsa::PairWalkRec> rec(nb);
-            std::memset(rec.data(), 0, nb * sizeof(gsa::PairWalkRec));
-            std::vector<gsa::BatchPairState> state(nb);
-            for (size_t b = 0; b < nb; ++b)
-            {
-                rec[b].i = (int)bp[b].iEnd;
-                rec[b].j = (int)bp[b].jEnd;
-                rec[b].state = 4u;
-                state[b].tHi = gsa::pair_strips(TR, bp[b].iEnd) - 1;
-                state[b].J = bp[b].jEnd;
-                inf.strips += (int32_t)(state[b].tHi + 1);
-            }
-            if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(gsa::PairWalkRec), hipMemcpyHostToDevice, st)) != hipSuccess ||
-                (e = hipStreamSynchronize(st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            std::vector<gsa::BatchChunk> chunks;
-            std::vector<gsa::PairBatchTask> tasks;
-            std::vector<gsa::PairBatchDesc> descs;
-            std::vector<gsa::PairBatchWalk> walks;
-            std::vector<char> blob;
-            for (;;)
-            {
-                const long long used = gsa::batch_plan_round(TR, limit, state, &chunks);
-                if (chunks.empty())
-                {
-                    for (const gsa::BatchPairState& s : state)
-                        if (s.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
-                    break;
-                }
-                int s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096);
-                if (s != GSA_SUCCESS) return s;
-                unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
-                tasks.clear();
-                descs.clear();
-                walks.clear();
-                for (size_t c = 0; c < chunks.size(); ++c)
-                {
-                    const gsa::BatchChunk& ch = chunks[c];
-                    const Bp& B = bp[(size_t)ch.pair];
-                    const gsa_pair_dev& P = pairs[B.p];
-                    gsa::PairBatchDesc d;
-                    std::memset(&d, 0, sizeof(d));
-                    d.seqY = P.seqY;
-                    d.seqX = P.seqX;
-                    d.R = P.adjrows - 1;
-                    d.iEnd = (int)B.iEnd;
-                    d.J = (int)ch.c.J;
-                    d.granBase = route.granOff[(size_t)B.k];
-                    d.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
-                    d.stripBytes = ch.c.stripBytes;
-                    descs.push_back(d);
-                    for (long long t = ch.c.tLo; t <= ch.c.tHi; ++t)
-                    {
-                        gsa::PairBatchTask k;
-                        k.pair = (int)c;
-                        k.strip = (int)t;
-                        k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, t);
-                        tasks.push_back(k);
-                    }
-                    gsa::PairBatchWalk w;
-                    std::memset(&w, 0, sizeof(w));
-                    w.seqY = P.seqY;
-                    w.seqX = P.seqX;
-                    w.codes = dcodes + ch.codeOff;
-                    w.stripBytes = ch.c.stripBytes;
-                    w.tLo = (int)ch.c.tLo;
-                    w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
-                    w.rec = ch.pair;
-                    w.moves = dmoves + B.movOff;
-                    walks.push_back(w);
-                }
-                // the longest chains first
-                std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
-                    return descs[(size_t)a.pair].J > descs[(size_t)b.pair].J;
-                });
-                // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
-                const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
-                             oWalk = oDesc + descs.size() * sizeof(gsa::PairBatchDesc),
-                             tabBytes = oWalk + walks.size() * sizeof(gsa::PairBatchWalk);
-                if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
-                char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
-                blob.assign(tabBytes, 0);
-                std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
-                std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(gsa::PairBatchDesc));
-                std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(gsa::PairBatchWalk));
-                if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                gsa::PairBatchFillArgs f;
-                std::memset(&f, 0, sizeof(f));
-                f.pairs = (const gsa::PairBatchDesc*)(dtab + oDesc);
-                f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
-                f.ntasks = (int)tasks.size();
-                f.subst = subst;
-                f.substsz = substsz;
-                f.go = gapo;
-                f.ge = gape;
-                f.gran = dgran;
-                f.gran2 = dgran + route.granTotal;
-                f.codes = dcodes;
-                f.counter = (unsigned*)dtab;
-                gsa::PairBatchWalkArgs w;
-                std::memset(&w, 0, sizeof(w));
-                w.walks = (const gsa::PairBatchWalk*)(dtab + oWalk);
-                w.nwalks = (int)walks.size();
-                w.krShift = KR == 8 ? 3 : 4;
-                w.local = local ? 1 : 0;
-                w.recs = drec;
-                int grid = 1;
-                const int walkGrid = max_workgroups > 0 ? std::min(w.nwalks, (int)max_workgroups) : w.nwalks;
-                if ((e = gsa::pair_batch_fill_grid(w.local, gapo != gape, KR, f.ntasks, max_workgroups, &grid)) != hipSuccess ||
-                    (e = gsa::launch_pair_batch_trace(f, w.local, w, KR, grid, walkGrid, ctx->adbev, st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                note_launch(ctx);
-                if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(gsa::PairWalkRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                    (e = hipStreamSynchronize(st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                float m0 = 0.f, m1 = 0.f;
-                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-                inf.fill_ms += m0;
-                inf.walk_ms += m1;
-                inf.rounds += 1;
-                inf.strips_filled += (int32_t)tasks.size();
-                inf.code_bytes = std::max<int64_t>(inf.code_bytes, used);
-                // every record that came back: in range, and done or on its chunk's upper boundary
-                for (const gsa::BatchChunk& ch : chunks)
-                {
-                    const Bp& B = bp[(size_t)ch.pair];
-                    const gsa::PairWalkRec& r = rec[(size_t)ch.pair];
-                    gsa::BatchPairState& S = state[(size_t)ch.pair];
-                    if (r.n < 0 || r.n > B.iEnd + B.jEnd || r.i < 0 || r.i > B.iEnd || r.j < 0 || r.j > ch.c.J)
-                        return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                    if (r.done)
-                    {
-                        S.tHi = -1;
-                        continue;
-                    }
-                    if (ch.c.tLo < 1 || r.i != gsa::pair_chunk_stop_row(TR, ch.c) || r.j < 1)
-                        return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                    S.tHi = ch.c.tLo - 1;
-                    S.J = r.j;
-                }
-            }
-            std::vector<unsigned char> mv((size_t)movTotal + 1);
-            if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                (e = hipStreamSynchronize(st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            for (size_t b = 0; b < nb; ++b)
-            {
-                gsa_align_db_result& r = res[(size_t)bp[b].p];
-                cig[(size_t)bp[b].p] = fold_cigar(mv.data() + bp[b].movOff, rec[b].n);
-                r.i_start = rec[b].i;
-                r.j_start = rec[b].j;
-                r.status = 0;
-            }
+            const BatchTrace t {pairs, subst, substsz, gapo, gape, local, max_workgroups, KR, route.granTotal, limit};
+            const int s = trace_batch<GlobalBatchTrace>(ctx, t, bp, &inf, res.data(), cig.data(), st);
+            if (s != GSA_SUCCESS) return s;
         }
         // the pairs that went alone, after the rounds: this overwrites kBufGran and the kBufPair* slots
         std::sort(alone.begin(), alone.end());
@@ -2556,28 +2686,7 @@ int align_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, co
             res[(size_t)p].cigar_off = res[(size_t)p].cigar_len = 0;
         }
     }
-    // the strings back to back in pair order; a pair's offset does not depend on the buffer's size
-    int64_t at = 0;
-    for (int p = 0; p < npairs; ++p)
-    {
-        gsa_align_db_result& r = res[(size_t)p];
-        const int64_t len = (int64_t)cig[(size_t)p].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
-        out[p] = r;
-    }
-    if (cigar_need) *cigar_need = at;
-    if (info) *info = inf;
+    finish_batch(res, cig, inf, out, cigar, cigar_cap, cigar_need, info);
     if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms + other_ms;
     return GSA_SUCCESS;
 }
@@ -2743,11 +2852,35 @@ int score_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const in
 }
 
 
+// gsa_align_pair_semi_dev's unit (nw_pair_semi_trace.hip): rows 1 ... R over the columns of the window.
+// The walk never leaves the window (the bound excludes it) and ends in row 0.
+struct SemiTrace
+{
+    using FillArgs = gsa::SemiFillArgs;
+    using WalkArgs = gsa::SemiWalkArgs;
+    using WalkRec = gsa::SemiWalkRec;
+    static void mode_args(const PairTrace& t, FillArgs& f, WalkArgs& w)
+    {
+        f.R = (int)t.R;
+        f.jW = w.jW = (int)t.jW;
+    }
+    static hipError_t launch(const PairTrace& t, const FillArgs& f, const WalkArgs& w, hipEvent_t* ev, hipStream_t st)
+    {
+        int grid = 1;
+        const hipError_t e = gsa::semi_fill_grid(t.gapo != t.gape, t.KR, f.nstrips, &grid);
+        return e != hipSuccess ? e : gsa::launch_semi_trace(f, w, t.KR, grid, ev, st);
+    }
+    static bool rec_ok(const PairTrace&, const gsa::PairChunk&, const WalkRec& r) { return !r.left; }
+    static bool go_on(const PairTrace& t, int64_t TR, const gsa::PairChunk& ch, const WalkRec& r)
+    {
+        return ch.tLo >= 1 && r.i == gsa::pair_chunk_stop_row(TR, ch) && r.j > t.jW && r.j <= t.jW + ch.J;
+    }
+    static bool end_ok(const WalkRec& r) { return r.i == 0; }
+};
+
 // gsa_align_pair_semi_dev: score and end column from semi_pair_score, whose checkpoint rows stay in
-// kBufGran; the column window from the score (nw_pair_semi_plan.h); then, bottom-up from row R's strip
-// to strip 0, chunks of strips whose windowed move codes fit scratch_limit, a fill and a walk launch
-// per chunk and one small copy of the walk's record back (nw_pair_semi_trace.hip); at the end the
-// move bytes, folded into the CIGAR.  gsa_last_launch's record is left as it was.
+// kBufGran; the column window from the score (nw_pair_semi_plan.h); then trace_pair from (R, j_end) over
+// the window, up to row 0.  gsa_last_launch's record is left as it was.
 int align_pair_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                          const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
                          gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -2785,7 +2918,6 @@ int align_pair_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, con
         if ((s = semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, true, &sr, st, &route)) != GSA_SUCCESS)
             return s;
         const KeepLaunchRecord keep(ctx);
-        hipError_t e = hipSuccess;
         inf.score_ms = sr.calc_kernel_ms;
         r.score = sr.score;
         r.i_end = R;
@@ -2805,106 +2937,11 @@ int align_pair_semi_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, con
             gsa::PairChunk ch;
             // (a limit below one strip's windowed codes: known only once the score is)
             if (!gsa::semi_plan_chunk(TR, strips - 1, jEnd, jW, limit, &ch)) return GSA_ERROR_INVALID_VALUE;
-            if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
-                (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(R + jEnd - jW), 4096)) != GSA_SUCCESS)
-                return s;
-            for (hipEvent_t& ev : ctx->adbev)
-                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-            char* const meta = ctx->buf[kBufPairMeta].as<char>();
-            gsa::SemiWalkRec* const drec = (gsa::SemiWalkRec*)(meta + 64);
-            const size_t stride = (size_t)gsa::gran_stride((int)C);
-            gsa::SemiWalkRec rec;
-            std::memset(&rec, 0, sizeof(rec));
-            rec.i = (int)R;
-            rec.j = (int)jEnd;
-            rec.state = 4u;
-            if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            for (;;)
-            {
-                const int nstrips = (int)(ch.tHi - ch.tLo + 1);
-                const int64_t J = jW + ch.J;  // the chunk's last column
-                if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
-                if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                gsa::SemiFillArgs f;
-                std::memset(&f, 0, sizeof(f));
-                f.seqY = seqY;
-                f.seqX = seqX;
-                f.subst = subst;
-                f.substsz = substsz;
-                f.go = gapo;
-                f.ge = gape;
-                f.R = (int)R;
-                f.jW = (int)jW;
-                f.J = (int)J;
-                f.tLo = (int)ch.tLo;
-                f.nstrips = nstrips;
-                f.gran = ctx->buf[kBufGran].as<unsigned long long>();
-                f.gran2 = f.gran + (size_t)route.tickets * stride;
-                f.granStride = (long long)stride;
-                f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
-                f.stripBytes = ch.stripBytes;
-                f.counter = (unsigned*)meta;
-                gsa::SemiWalkArgs w;
-                std::memset(&w, 0, sizeof(w));
-                w.seqY = seqY;
-                w.seqX = seqX;
-                w.codes = f.codes;
-                w.stripBytes = ch.stripBytes;
-                w.krShift = KR == 8 ? 3 : 4;
-                w.tLo = (int)ch.tLo;
-                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
-                w.jW = (int)jW;
-                w.rec = drec;
-                w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
-                int grid = 1;
-                if ((e = gsa::semi_fill_grid(gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
-                    (e = gsa::launch_semi_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                note_launch(ctx);
-                if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                    (e = hipStreamSynchronize(st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                float m0 = 0.f, m1 = 0.f;
-                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-                inf.fill_ms += m0;
-                inf.walk_ms += m1;
-                inf.chunks += 1;
-                inf.strips_filled += nstrips;
-                inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
-                // the walk left the window (the bound excludes it), or wrote past its moves
-                if (rec.left || rec.n < 0 || rec.n > R + jEnd - jW) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                if (rec.done) break;
-                // on the chunk's upper boundary: the next chunk, for the columns up to here
-                if (ch.tLo < 1 || rec.i != w.iStop || rec.j <= jW || rec.j > J ||
-                    !gsa::semi_plan_chunk(TR, ch.tLo - 1, rec.j, jW, limit, &ch))
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            }
-            if (rec.i != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            std::vector<unsigned char> mv((size_t)rec.n + 1);
-            if (rec.n > 0 &&
-                ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                 (e = hipStreamSynchronize(st)) != hipSuccess))
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            cig = fold_cigar(mv.data(), rec.n);
-            r.i_start = 0;
-            r.j_start = rec.j;
+            const PairTrace t {seqY, seqX, subst, substsz, gapo, gape, 0, R, C, R, jEnd, jW, KR, route.tickets, limit};
+            if ((s = trace_pair<SemiTrace>(ctx, t, ch, &inf, &r, &cig, st)) != GSA_SUCCESS) return s;
         }
     }
-    const int64_t len = (int64_t)cig.size();
-    if (len + 1 <= cigar_cap)
-    {
-        std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
-        r.cigar_len = len;
-    }
-    else
-        r.status = 2;
-    if (cigar_need) *cigar_need = len + 1;
-    *out = r;
-    if (info) *info = inf;
-    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
-    return GSA_SUCCESS;
+    return finish_pair(r, cig, inf, out, cigar, cigar_cap, cigar_need, info, kernel_ms);
 }
 
 
@@ -2930,11 +2967,34 @@ int score_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const
     return semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, false, out, st, nullptr, true);
 }
 
+// gsa_align_pair_overlap_dev's unit (nw_pair_overlap_trace.hip): rows 1 ... iEnd from column 1.  The walk
+// ends as soon as it stands on row 0 or on column 0, whatever strips lie above.
+struct OverlapTrace
+{
+    using FillArgs = gsa::OverlapFillArgs;
+    using WalkArgs = gsa::OverlapWalkArgs;
+    using WalkRec = gsa::OverlapWalkRec;
+    static void mode_args(const PairTrace& t, FillArgs& f, WalkArgs&) { f.iEnd = (int)t.iEnd; }
+    static hipError_t launch(const PairTrace& t, const FillArgs& f, const WalkArgs& w, hipEvent_t* ev, hipStream_t st)
+    {
+        int grid = 1;
+        const hipError_t e = gsa::overlap_fill_grid(t.gapo != t.gape, t.KR, f.nstrips, &grid);
+        return e != hipSuccess ? e : gsa::launch_overlap_trace(f, w, t.KR, grid, ev, st);
+    }
+    static bool rec_ok(const PairTrace& t, const gsa::PairChunk& ch, const WalkRec& r)
+    {
+        return r.i >= 0 && r.i <= t.iEnd && r.j >= 0 && r.j <= ch.J;
+    }
+    static bool go_on(const PairTrace&, int64_t TR, const gsa::PairChunk& ch, const WalkRec& r)
+    {
+        return gsa::overlap_walk_goes_on(TR, ch, r.i, r.j);
+    }
+    static bool end_ok(const WalkRec& r) { return r.i == 0 || r.j == 0; }
+};
+
 // gsa_align_pair_overlap_dev: score and end cell from semi_pair_score's overlap launch, whose checkpoint
-// rows stay in kBufGran; then, bottom-up from i_end's strip, chunks of strips whose move codes over the
-// columns up to where the walk stands fit scratch_limit, a fill and a walk launch per chunk and one
-// small copy of the walk's record back (nw_pair_overlap_trace.hip), until the walk stands on row 0 or on
-// column 0; at the end the move bytes, folded into the CIGAR.  gsa_last_launch's record is left as it was.
+// rows stay in kBufGran; then trace_pair from the end cell, bottom-up from i_end's strip, until the walk
+// stands on row 0 or on column 0.  gsa_last_launch's record is left as it was.
 int align_pair_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t* seqX, int32_t adjcols,
                             const int32_t* subst, int32_t substsz, int32_t gapo, int32_t gape, int64_t scratch_limit,
                             gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -2964,7 +3024,6 @@ int align_pair_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
         if ((s = semi_pair_score(ctx, seqY, R, seqX, C, subst, substsz, gapo, gape, true, &sr, st, &route, true)) != GSA_SUCCESS)
             return s;
         const KeepLaunchRecord keep(ctx);
-        hipError_t e = hipSuccess;
         inf.score_ms = sr.calc_kernel_ms;
         r.score = sr.score;
         r.i_end = r.i_start = sr.i_end;
@@ -2980,115 +3039,22 @@ int align_pair_overlap_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
             gsa::PairChunk ch;
             // (a limit below one strip's codes: known only once j_end is)
             if (!gsa::overlap_plan_chunk(TR, gsa::overlap_end_strip(TR, iEnd), jEnd, limit, &ch)) return GSA_ERROR_INVALID_VALUE;
-            if ((s = reserve_hard(ctx, ctx->buf[kBufPairMeta], 4096)) != GSA_SUCCESS ||
-                (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(iEnd + jEnd), 4096)) != GSA_SUCCESS)
-                return s;
-            for (hipEvent_t& ev : ctx->adbev)
-                if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-            char* const meta = ctx->buf[kBufPairMeta].as<char>();
-            gsa::OverlapWalkRec* const drec = (gsa::OverlapWalkRec*)(meta + 64);
-            const size_t stride = (size_t)gsa::gran_stride((int)C);
-            gsa::OverlapWalkRec rec;
-            std::memset(&rec, 0, sizeof(rec));
-            rec.i = (int)iEnd;
-            rec.j = (int)jEnd;
-            rec.state = 4u;
-            if ((e = hipMemcpyAsync(drec, &rec, sizeof(rec), hipMemcpyHostToDevice, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            for (;;)
-            {
-                const int nstrips = (int)(ch.tHi - ch.tLo + 1);
-                if ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)ch.codeBytes, 4096)) != GSA_SUCCESS) return s;
-                if ((e = hipMemsetAsync(meta, 0, 4, st)) != hipSuccess) return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-                gsa::OverlapFillArgs f;
-                std::memset(&f, 0, sizeof(f));
-                f.seqY = seqY;
-                f.seqX = seqX;
-                f.subst = subst;
-                f.substsz = substsz;
-                f.go = gapo;
-                f.ge = gape;
-                f.iEnd = (int)iEnd;
-                f.J = (int)ch.J;
-                f.tLo = (int)ch.tLo;
-                f.nstrips = nstrips;
-                f.gran = ctx->buf[kBufGran].as<unsigned long long>();
-                f.gran2 = f.gran + (size_t)route.tickets * stride;
-                f.granStride = (long long)stride;
-                f.codes = ctx->buf[kBufPairCodes].as<unsigned char>();
-                f.stripBytes = ch.stripBytes;
-                f.counter = (unsigned*)meta;
-                gsa::OverlapWalkArgs w;
-                std::memset(&w, 0, sizeof(w));
-                w.seqY = seqY;
-                w.seqX = seqX;
-                w.codes = f.codes;
-                w.stripBytes = ch.stripBytes;
-                w.krShift = KR == 8 ? 3 : 4;
-                w.tLo = (int)ch.tLo;
-                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch);
-                w.rec = drec;
-                w.moves = ctx->buf[kBufPairMoves].as<unsigned char>();
-                int grid = 1;
-                if ((e = gsa::overlap_fill_grid(gapo != gape, KR, nstrips, &grid)) != hipSuccess ||
-                    (e = gsa::launch_overlap_trace(f, w, KR, grid, ctx->adbev, st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                note_launch(ctx);
-                if ((e = hipMemcpyAsync(&rec, drec, sizeof(rec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                    (e = hipStreamSynchronize(st)) != hipSuccess)
-                    return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-                float m0 = 0.f, m1 = 0.f;
-                (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-                (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-                inf.fill_ms += m0;
-                inf.walk_ms += m1;
-                inf.chunks += 1;
-                inf.strips_filled += nstrips;
-                inf.code_bytes = std::max<int64_t>(inf.code_bytes, ch.codeBytes);
-                // a record out of range, or moves written past their buffer
-                if (rec.n < 0 || rec.n > iEnd + jEnd || rec.i < 0 || rec.i > iEnd || rec.j < 0 || rec.j > ch.J)
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                if (rec.done) break;
-                // on the chunk's upper boundary: the next chunk, for the columns up to here
-                if (!gsa::overlap_walk_goes_on(TR, ch, rec.i, rec.j) ||
-                    !gsa::overlap_plan_chunk(TR, ch.tLo - 1, rec.j, limit, &ch))
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            }
-            if (rec.i != 0 && rec.j != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            std::vector<unsigned char> mv((size_t)rec.n + 1);
-            if (rec.n > 0 &&
-                ((e = hipMemcpyAsync(mv.data(), ctx->buf[kBufPairMoves].p, (size_t)rec.n, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                 (e = hipStreamSynchronize(st)) != hipSuccess))
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            cig = fold_cigar(mv.data(), rec.n);
-            r.i_start = rec.i;
-            r.j_start = rec.j;
+            const PairTrace t {seqY, seqX, subst, substsz, gapo, gape, 0, R, C, iEnd, jEnd, 0, KR, route.tickets, limit};
+            if ((s = trace_pair<OverlapTrace>(ctx, t, ch, &inf, &r, &cig, st)) != GSA_SUCCESS) return s;
         }
     }
-    const int64_t len = (int64_t)cig.size();
-    if (len + 1 <= cigar_cap)
-    {
-        std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
-        r.cigar_len = len;
-    }
-    else
-        r.status = 2;
-    if (cigar_need) *cigar_need = len + 1;
-    *out = r;
-    if (info) *info = inf;
-    if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
-    return GSA_SUCCESS;
+    return finish_pair(r, cig, inf, out, cigar, cigar_cap, cigar_need, info, kernel_ms);
 }
 
 
-// What score_semi_batch_impl's launch ran (gsa_align_batch_semi_dev reads the checkpoint rows it left
-// in kBufGran: pair p's row t at granOff[p] + t gran_stride(C), the affine second array granTotal
-// words behind).
+// What score_semi_batch_impl's launch ran (gsa_align_batch_semi_dev and gsa_align_batch_overlap_dev read
+// the checkpoint rows it left in kBufGran: pair p's row t at granOff[p] + t gran_stride(C), the affine
+// second array granTotal words behind).
 struct SemiBatchRoute
 {
     int K = 0;                       // rows per lane of the K-rows launch; 0: nothing was launched
     long long granTotal = 0;         // words of the first array, over all pairs
-    long long pmax = 0;              // max(0, largest table value): the windows' bound (nw_pair_semi_plan.h)
+    long long pmax = 0;              // max(0, largest table value): the windows' bound (nw_pair_semi_plan.h); overlap: unused
     std::vector<int> tickets;        // per pair of the call: its tickets (0: an empty side)
     std::vector<long long> granOff;  // its first row, in words
 };
@@ -3097,11 +3063,16 @@ struct SemiBatchRoute
 // on the host; for the others the range tests of a mode without a second path, per pair, then the
 // batched semi-global instances of the K-rows score kernel in one launch (every pair's row R into its
 // own part of kBufBidi, PairDesc::score) and one workgroup per pair that takes the row's first maximum;
-// one copy brings every score and end column back.  gsa_last_launch's record and the fills' sticky
-// error word are left alone.
+// one copy brings every score and end column back.  The answers, the host's included, are written once
+// nothing can refuse the call any more: a refusal leaves out as it was.  gsa_last_launch's record and
+// the fills' sticky error word are left alone.
+// overlap (gsa_score_overlap_batch_dev): the same tests and geometry on the batched overlap instances,
+// which store column C of every row of every one of a pair's tickets into its own part of kBufOvCol
+// (PairDesc::hcol) as well; the workgroup behind them takes the first maximum over row R and column C
+// and brings the end cell's row back too.  An empty side scores 0 at (R, 0).
 int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                           int32_t gapo, int32_t gape, bool forAlign, gsa_score_result* out, float* batch_ms, hipStream_t st,
-                          SemiBatchRoute* route = nullptr)
+                          SemiBatchRoute* route = nullptr, bool overlap = false)
 {
     if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
     if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
@@ -3115,22 +3086,28 @@ int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
         route->tickets.assign((size_t)npairs, 0);
         route->granOff.assign((size_t)npairs, 0);
     }
-    // an empty side, answered on the host as score_semi_impl answers it
     std::vector<int> bp;
     for (int p = 0; p < npairs; ++p)
-    {
-        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
-        out[p].calc_kernel_ms = 0.f;
-        if (R == 0 || C == 0)
+        if (pairs[p].adjrows > 1 && pairs[p].adjcols > 1) bp.push_back(p);
+    // an empty side, answered on the host as score_semi_impl and score_overlap_impl answer it
+    auto host_pairs = [&]() {
+        for (int p = 0; p < npairs; ++p)
         {
-            out[p].score = R == 0 ? 0 : (int32_t)(gapo + (R - 1) * gape);
-            out[p].i_end = R;
-            out[p].j_end = 0;
+            const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
+            out[p].calc_kernel_ms = 0.f;
+            if (R == 0 || C == 0)
+            {
+                out[p].score = (overlap || R == 0) ? 0 : (int32_t)(gapo + (R - 1) * gape);
+                out[p].i_end = R;
+                out[p].j_end = 0;
+            }
         }
-        else
-            bp.push_back(p);
+    };
+    if (bp.empty())
+    {
+        host_pairs();
+        return GSA_SUCCESS;
     }
-    if (bp.empty()) return GSA_SUCCESS;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
     std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
@@ -3151,8 +3128,8 @@ int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
     const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
     const int nb = (int)bp.size();
     std::vector<gsa::PairDesc> hd;
-    std::vector<long long> rowOff;  // ints: the pair's row within kBufBidi, a multiple of 16
-    long long tickets = 0, gran = 0, rowInts = 0;
+    std::vector<long long> rowOff, colOff;  // ints: the pair's row within kBufBidi (a multiple of 16), its column within kBufOvCol
+    long long tickets = 0, gran = 0, rowInts = 0, colInts = 0;
     for (int p : bp)
     {
         const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
@@ -3180,13 +3157,24 @@ int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
         // row R: columns -kTapPad .. C + 79, as the tap rows
         rowOff.push_back(rowInts);
         rowInts += ((long long)gsa::kTapPad + C + 80 + 15) & ~15ll;
+        // overlap, column C: the rows 0 ... nTickets TR -- every strip of every ticket stores its K words per
+        // lane, rows past R included, so the pair's last ticket counts whole; a column starts at a multiple
+        // of 16 ints, which keeps every store the alignment it has in the single call
+        colOff.push_back(colInts);
+        colInts += (1 + (long long)d.nTickets * TR + 15) & ~15ll;
         hd.push_back(d);
     }
     // every buffer before anything is launched
     int s;
     if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], (size_t)rowInts * sizeof(int))) != GSA_SUCCESS) return s;
+    if (overlap && (s = reserve_hard(ctx, ctx->buf[kBufOvCol], (size_t)colInts * sizeof(int))) != GSA_SUCCESS) return s;
     int* const rows = ctx->buf[kBufBidi].as<int>();
-    for (int i = 0; i < nb; ++i) hd[(size_t)i].score = rows + rowOff[(size_t)i];
+    int* const cols = overlap ? ctx->buf[kBufOvCol].as<int>() : nullptr;
+    for (int i = 0; i < nb; ++i)
+    {
+        hd[(size_t)i].score = rows + rowOff[(size_t)i];
+        if (overlap) hd[(size_t)i].hcol = cols + colOff[(size_t)i];
+    }
     if ((s = ensure_gran(ctx, 2 * (size_t)gran, st)) != GSA_SUCCESS) return s;
     if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
     // two result words per pair (unused by these modes), then the answers and the error word's
@@ -3230,23 +3218,26 @@ int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
     a.err = (unsigned*)(sctl + 3);  // the score kernels' own error word (score_ag_strip)
     a.spin = ctx->spin_ticks;
     a.swBest = res;
-    a.rowR = rows;  // (every pair's own row comes from its descriptor)
+    a.rowR = rows;  // (every pair's own row and column come from its descriptor)
+    a.tapH = cols;  // (overlap; no tap: tapRow stays 0)
     a.epoch = ++ctx->epoch;
     if (a.epoch == 0) a.epoch = ++ctx->epoch;
     if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess ||
         (e = hipMemsetAsync(res, 0, resBytes, st)) != hipSuccess)
         return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
     (void)hipEventRecord(ctx->ev0, st);
-    const int mode = gapo == gape ? gsa::kModeScoreSGL : gsa::kModeScoreSG;
+    const bool linear = gapo == gape;
+    const int mode = overlap ? (linear ? gsa::kModeScoreOVL : gsa::kModeScoreOV) : (linear ? gsa::kModeScoreSGL : gsa::kModeScoreSG);
     // the int8 profile for linear gaps only, as score_batch_impl picks it.  GSA_KROW_Q8=0 / 2: int16 / int8 always
     const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
-    a.q8 = (q8env != 0 && (q8env == 2 || mode == gsa::kModeScoreSGL) &&
-            gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
+    a.q8 = (q8env != 0 && (q8env == 2 || linear) && gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
     a.q8flag = ctx->ctl + 2;
     // one pair: one workgroup per CU (its tickets are a chain); a batch: all resident slots
     const int grid = nb == 1 ? std::max(1, std::min((int)tickets, ctx->cu_count)) : 0;
-    if ((e = gsa::launch_krow_score_semi_batch(a, mode, scoreK, grid, st)) != hipSuccess ||
-        (e = gsa::launch_semi_rowmax_batch(ddesc, nb, gapo, gape, a.err, dout, st)) != hipSuccess)
+    if (overlap ? ((e = gsa::launch_krow_score_overlap_batch(a, mode, scoreK, grid, st)) != hipSuccess ||
+                   (e = gsa::launch_overlap_max_batch(ddesc, nb, gapo, gape, a.err, dout, st)) != hipSuccess)
+                : ((e = gsa::launch_krow_score_semi_batch(a, mode, scoreK, grid, st)) != hipSuccess ||
+                   (e = gsa::launch_semi_rowmax_batch(ddesc, nb, gapo, gape, a.err, dout, st)) != hipSuccess))
         return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
     note_launch(ctx);
     (void)hipEventRecord(ctx->ev1, st);
@@ -3258,24 +3249,55 @@ int score_semi_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     if (batch_ms) *batch_ms = ms;
     if ((unsigned)ho[(size_t)nb].score != 0) return GSA_ERROR_KERNEL_FAILURE;
+    // semi-global: a column of row R; overlap: a cell of row R or of column C, and never a negative score
     for (int i = 0; i < nb; ++i)
     {
         const gsa::ScoreOut& o = ho[(size_t)i];
-        if (o.j_end < 0 || o.j_end > hd[(size_t)i].C) return GSA_ERROR_KERNEL_FAILURE;
+        const int R = hd[(size_t)i].R, C = hd[(size_t)i].C;
+        if (o.j_end < 0 || o.j_end > C) return GSA_ERROR_KERNEL_FAILURE;
+        if (overlap && (o.score < 0 || o.i_end < 0 || o.i_end > R || (o.i_end != R && o.j_end != C))) return GSA_ERROR_KERNEL_FAILURE;
+    }
+    host_pairs();
+    for (int i = 0; i < nb; ++i)
+    {
+        const gsa::ScoreOut& o = ho[(size_t)i];
         gsa_score_result& r = out[bp[(size_t)i]];
         r.score = o.score;
-        r.i_end = hd[(size_t)i].R;
+        r.i_end = overlap ? o.i_end : hd[(size_t)i].R;
         r.j_end = o.j_end;
     }
     return GSA_SUCCESS;
 }
 
+// gsa_align_batch_semi_dev's unit (nw_pair_semi_trace_batch.hip): every pair over its own window; a
+// finished walk stands in row 0
+struct SemiBatchTrace
+{
+    using Desc = gsa::SemiBatchDesc;
+    using Walk = gsa::SemiBatchWalk;
+    using FillArgs = gsa::SemiBatchFillArgs;
+    using WalkArgs = gsa::SemiBatchWalkArgs;
+    using WalkRec = gsa::SemiWalkRec;
+    static gsa::PairBatchDesc& base(Desc& d) { return d.p; }
+    static void window(const BatchTracePair& B, Desc& d, Walk& w) { d.jW = w.jW = (int)B.jW; }
+    static hipError_t launch(const BatchTrace& t, const FillArgs& f, const WalkArgs& w, int walkGrid, hipEvent_t* ev, hipStream_t st)
+    {
+        int grid = 1;
+        const hipError_t e = gsa::semi_batch_fill_grid(t.gapo != t.gape, t.KR, f.ntasks, t.max_workgroups, &grid);
+        return e != hipSuccess ? e : gsa::launch_semi_batch_trace(f, w, t.KR, grid, walkGrid, ev, st);
+    }
+    static bool rec_ok(const WalkRec& r) { return !r.left; }
+    static bool advance(long long TR, const gsa::PairChunk& c, long long i, long long j, bool done, gsa::BatchPairState* s)
+    {
+        return gsa::semi_batch_advance(TR, c, i, j, done, s);
+    }
+};
+
 // gsa_align_batch_semi_dev: every pair's score and end column from score_semi_batch_impl, whose
 // checkpoint rows stay in kBufGran, every pair in its own granules; each pair's column window from its
-// own score (nw_pair_semi_plan.h); then rounds that fit scratch_limit, one fill launch over the strips
-// of many pairs, one walk launch with a wave per pair and one small copy back per round
-// (nw_pair_semi_trace_batch_plan.h, nw_pair_semi_trace_batch.hip); at the end the move bytes of all
-// pairs in one copy, folded into the CIGARs.  gsa_last_launch's record is left as it was.
+// own score (nw_pair_semi_plan.h); then trace_batch over the pairs with a path right of column 0 whose
+// one strip fits the limit (the others: the host's answer, or status 1).  gsa_last_launch's record is
+// left as it was.
 int align_batch_semi_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                           int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
                           gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -3299,24 +3321,15 @@ int align_batch_semi_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
     const KeepLaunchRecord keep(ctx);
     SemiBatchRoute route;
     std::vector<gsa_score_result> sres((size_t)npairs);
-    {
-        const int s = score_semi_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, true, sres.data(), &inf.score_ms,
-                                            st, &route);
-        if (s != GSA_SUCCESS) return s;
-    }
+    int s = score_semi_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, true, sres.data(), &inf.score_ms, st, &route);
+    if (s != GSA_SUCCESS) return s;
     const int K = route.K;
     const int KR = K * gsa::kSparseNS;
     const int64_t TR = 64 * (int64_t)KR;
     inf.strip_rows = (int32_t)TR;                   // (0: every pair has an empty side)
     inf.gran_bytes = 16 * (int64_t)route.granTotal;  // both arrays, 8-byte words
     // the traced pairs: letters on both sides, an end cell right of column 0, one strip within the limit
-    struct Bp
-    {
-        int p;  // index into pairs
-        int64_t R, jEnd, jW, movOff;
-    };
-    std::vector<Bp> bp;
-    int64_t movTotal = 0;
+    std::vector<BatchTracePair> bp;
     for (int p = 0; p < npairs; ++p)
     {
         const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
@@ -3338,432 +3351,49 @@ int align_batch_semi_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pair
             r.status = 1;  // one strip's windowed codes exceed the limit: score and end cell only
             continue;
         }
-        bp.push_back(Bp {p, R, r.j_end, jW, movTotal});
-        movTotal += R + r.j_end - jW;
+        bp.push_back(BatchTracePair {p, R, r.j_end, jW, route.granOff[(size_t)p]});
         inf.window_cols += r.j_end - jW;
     }
     if (!bp.empty())
     {
-        hipError_t e = hipSuccess;
-        const size_t nb = bp.size();
-        inf.batch_pairs = (int32_t)nb;
-        int sr;
-        if ((sr = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
-            (sr = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(gsa::SemiWalkRec), 4096)) != GSA_SUCCESS)
-            return sr;
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-        gsa::SemiWalkRec* const drec = ctx->buf[kBufPairBatchRec].as<gsa::SemiWalkRec>();
-        unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
-        const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
-        std::vector<gsa::SemiWalkRec> rec(nb);
-        std::memset(rec.data(), 0, nb * sizeof(gsa::SemiWalkRec));
-        std::vector<gsa::SemiBatchPairState> state(nb);
-        for (size_t b = 0; b < nb; ++b)
-        {
-            rec[b].i = (int)bp[b].R;
-            rec[b].j = (int)bp[b].jEnd;
-            rec[b].state = 4u;
-            state[b].tHi = gsa::pair_strips(TR, bp[b].R) - 1;
-            state[b].J = bp[b].jEnd;
-            state[b].jW = bp[b].jW;
-            inf.strips += (int32_t)(state[b].tHi + 1);
-        }
-        if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(gsa::SemiWalkRec), hipMemcpyHostToDevice, st)) != hipSuccess ||
-            (e = hipStreamSynchronize(st)) != hipSuccess)
-            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        std::vector<gsa::SemiBatchChunk> chunks;
-        std::vector<gsa::PairBatchTask> tasks;
-        std::vector<gsa::SemiBatchDesc> descs;
-        std::vector<gsa::SemiBatchWalk> walks;
-        std::vector<char> blob;
-        for (;;)
-        {
-            const long long used = gsa::semi_batch_plan_round(TR, limit, state, &chunks);
-            if (chunks.empty())
-            {
-                for (const gsa::SemiBatchPairState& s : state)
-                    if (s.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
-                break;
-            }
-            int s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096);
-            if (s != GSA_SUCCESS) return s;
-            unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
-            tasks.clear();
-            descs.clear();
-            walks.clear();
-            for (size_t c = 0; c < chunks.size(); ++c)
-            {
-                const gsa::SemiBatchChunk& ch = chunks[c];
-                const Bp& B = bp[(size_t)ch.pair];
-                const gsa_pair_dev& P = pairs[B.p];
-                gsa::SemiBatchDesc d;
-                std::memset(&d, 0, sizeof(d));
-                d.p.seqY = P.seqY;
-                d.p.seqX = P.seqX;
-                d.p.R = (int)B.R;
-                d.p.iEnd = (int)B.R;
-                d.p.J = (int)(B.jW + ch.c.J);  // the chunk's last column
-                d.p.granBase = route.granOff[(size_t)B.p];
-                d.p.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
-                d.p.stripBytes = ch.c.stripBytes;
-                d.jW = (int)B.jW;
-                descs.push_back(d);
-                for (long long t = ch.c.tLo; t <= ch.c.tHi; ++t)
-                {
-                    gsa::PairBatchTask k;
-                    k.pair = (int)c;
-                    k.strip = (int)t;
-                    k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, t);
-                    tasks.push_back(k);
-                }
-                gsa::SemiBatchWalk w;
-                std::memset(&w, 0, sizeof(w));
-                w.seqY = P.seqY;
-                w.seqX = P.seqX;
-                w.codes = dcodes + ch.codeOff;
-                w.stripBytes = ch.c.stripBytes;
-                w.tLo = (int)ch.c.tLo;
-                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
-                w.rec = ch.pair;
-                w.jW = (int)B.jW;
-                w.moves = dmoves + B.movOff;
-                walks.push_back(w);
-            }
-            // the longest chains first
-            std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
-                return chunks[(size_t)a.pair].c.J > chunks[(size_t)b.pair].c.J;
-            });
-            // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
-            const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
-                         oWalk = oDesc + descs.size() * sizeof(gsa::SemiBatchDesc),
-                         tabBytes = oWalk + walks.size() * sizeof(gsa::SemiBatchWalk);
-            if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
-            char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
-            blob.assign(tabBytes, 0);
-            std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
-            std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(gsa::SemiBatchDesc));
-            std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(gsa::SemiBatchWalk));
-            if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            gsa::SemiBatchFillArgs f;
-            std::memset(&f, 0, sizeof(f));
-            f.pairs = (const gsa::SemiBatchDesc*)(dtab + oDesc);
-            f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
-            f.ntasks = (int)tasks.size();
-            f.subst = subst;
-            f.substsz = substsz;
-            f.go = gapo;
-            f.ge = gape;
-            f.gran = dgran;
-            f.gran2 = dgran + route.granTotal;
-            f.codes = dcodes;
-            f.counter = (unsigned*)dtab;
-            gsa::SemiBatchWalkArgs w;
-            std::memset(&w, 0, sizeof(w));
-            w.walks = (const gsa::SemiBatchWalk*)(dtab + oWalk);
-            w.nwalks = (int)walks.size();
-            w.krShift = KR == 8 ? 3 : 4;
-            w.recs = drec;
-            int grid = 1;
-            const int walkGrid = max_workgroups > 0 ? std::min(w.nwalks, (int)max_workgroups) : w.nwalks;
-            if ((e = gsa::semi_batch_fill_grid(gapo != gape, KR, f.ntasks, max_workgroups, &grid)) != hipSuccess ||
-                (e = gsa::launch_semi_batch_trace(f, w, KR, grid, walkGrid, ctx->adbev, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            note_launch(ctx);
-            if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(gsa::SemiWalkRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                (e = hipStreamSynchronize(st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            float m0 = 0.f, m1 = 0.f;
-            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-            inf.fill_ms += m0;
-            inf.walk_ms += m1;
-            inf.rounds += 1;
-            inf.strips_filled += (int32_t)tasks.size();
-            inf.code_bytes = std::max<int64_t>(inf.code_bytes, used);
-            // every record that came back: in range, inside its window, and done in row 0 or on its
-            // chunk's upper boundary right of jW
-            for (const gsa::SemiBatchChunk& ch : chunks)
-            {
-                const Bp& B = bp[(size_t)ch.pair];
-                const gsa::SemiWalkRec& r = rec[(size_t)ch.pair];
-                gsa::SemiBatchPairState& S = state[(size_t)ch.pair];
-                if (r.left || r.n < 0 || r.n > B.R + B.jEnd - B.jW || r.i < 0 || r.i > B.R || r.j < 0 || r.j > B.jW + ch.c.J)
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                if (r.done)
-                {
-                    if (r.i != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                    S.tHi = -1;
-                    continue;
-                }
-                if (ch.c.tLo < 1 || r.i != gsa::pair_chunk_stop_row(TR, ch.c) || r.j <= B.jW)
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                S.tHi = ch.c.tLo - 1;
-                S.J = r.j;
-            }
-        }
-        std::vector<unsigned char> mv((size_t)movTotal + 1);
-        if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-            (e = hipStreamSynchronize(st)) != hipSuccess)
-            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        for (size_t b = 0; b < nb; ++b)
-        {
-            gsa_align_db_result& r = res[(size_t)bp[b].p];
-            cig[(size_t)bp[b].p] = fold_cigar(mv.data() + bp[b].movOff, rec[b].n);
-            r.i_start = 0;
-            r.j_start = rec[b].j;
-            r.status = 0;
-        }
+        const BatchTrace t {pairs, subst, substsz, gapo, gape, 0, max_workgroups, KR, route.granTotal, limit};
+        if ((s = trace_batch<SemiBatchTrace>(ctx, t, bp, &inf, res.data(), cig.data(), st)) != GSA_SUCCESS) return s;
     }
-    // the strings back to back in pair order; a pair's offset does not depend on the buffer's size
-    int64_t at = 0;
-    for (int p = 0; p < npairs; ++p)
-    {
-        gsa_align_db_result& r = res[(size_t)p];
-        const int64_t len = (int64_t)cig[(size_t)p].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
-        out[p] = r;
-    }
-    if (cigar_need) *cigar_need = at;
-    if (info) *info = inf;
+    finish_batch(res, cig, inf, out, cigar, cigar_cap, cigar_need, info);
     if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
     return GSA_SUCCESS;
 }
 
 
-// What score_overlap_batch_impl's launch ran (gsa_align_batch_overlap_dev reads the checkpoint rows it
-// left in kBufGran: pair p's row t at granOff[p] + t gran_stride(C), the affine second array granTotal
-// words behind).
-struct OverlapBatchRoute
+// gsa_align_batch_overlap_dev's unit (nw_pair_overlap_trace_batch.hip): gsa_align_batch_dev's descriptors;
+// a finished walk stands on row 0 or on column 0
+struct OverlapBatchTrace
 {
-    int K = 0;                       // rows per lane of the K-rows launch; 0: nothing was launched
-    long long granTotal = 0;         // words of the first array, over all pairs
-    std::vector<int> tickets;        // per pair of the call: its tickets (0: an empty side)
-    std::vector<long long> granOff;  // its first row, in words
+    using Desc = gsa::PairBatchDesc;
+    using Walk = gsa::OverlapBatchWalk;
+    using FillArgs = gsa::OverlapBatchFillArgs;
+    using WalkArgs = gsa::OverlapBatchWalkArgs;
+    using WalkRec = gsa::OverlapWalkRec;
+    static gsa::PairBatchDesc& base(Desc& d) { return d; }
+    static void window(const BatchTracePair&, Desc&, Walk&) {}
+    static hipError_t launch(const BatchTrace& t, const FillArgs& f, const WalkArgs& w, int walkGrid, hipEvent_t* ev, hipStream_t st)
+    {
+        int grid = 1;
+        const hipError_t e = gsa::overlap_batch_fill_grid(t.gapo != t.gape, t.KR, f.ntasks, t.max_workgroups, &grid);
+        return e != hipSuccess ? e : gsa::launch_overlap_batch_trace(f, w, t.KR, grid, walkGrid, ev, st);
+    }
+    static bool rec_ok(const WalkRec&) { return true; }
+    static bool advance(long long TR, const gsa::PairChunk& c, long long i, long long j, bool done, gsa::BatchPairState* s)
+    {
+        return gsa::overlap_batch_advance(TR, c, i, j, done, s);
+    }
 };
 
-// gsa_score_overlap_batch_dev: score_semi_batch_impl next to score_overlap_impl.  Pairs with an empty
-// side on the host (score 0 at (R, 0)); for the others semi_pair_score's range tests for the overlap
-// instances, per pair, then the batched overlap instances of the K-rows score kernel in one launch --
-// every pair's row R into its own part of kBufBidi (PairDesc::score), column C of every row of every one
-// of its tickets into its own part of kBufOvCol (PairDesc::hcol) -- and one workgroup per pair that takes
-// the first maximum over both; one copy brings every score and end cell back.  gsa_last_launch's record
-// and the fills' sticky error word are left alone.
-int score_overlap_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
-                             int32_t gapo, int32_t gape, bool forAlign, gsa_score_result* out, float* batch_ms, hipStream_t st,
-                             OverlapBatchRoute* route = nullptr)
-{
-    if (!ctx || !pairs || !subst || !out || npairs < 1) return GSA_ERROR_INVALID_VALUE;
-    if (substsz < 1 || substsz > 32) return GSA_ERROR_INVALID_VALUE;
-    if (gapo > gape || gape > 0) return GSA_ERROR_INVALID_VALUE;  // go <= ge <= 0
-    for (int p = 0; p < npairs; ++p)
-        if (pairs[p].adjrows < 1 || pairs[p].adjcols < 1 || !pairs[p].seqY || !pairs[p].seqX) return GSA_ERROR_INVALID_VALUE;
-    if (batch_ms) *batch_ms = 0.f;
-    if (route)
-    {
-        *route = OverlapBatchRoute {};
-        route->tickets.assign((size_t)npairs, 0);
-        route->granOff.assign((size_t)npairs, 0);
-    }
-    std::vector<int> bp;
-    for (int p = 0; p < npairs; ++p)
-        if (pairs[p].adjrows > 1 && pairs[p].adjcols > 1) bp.push_back(p);
-    // the answers are written once nothing can refuse the call any more: a refusal leaves out as it was
-    auto host_pairs = [&]() {
-        for (int p = 0; p < npairs; ++p)
-        {
-            const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
-            out[p].calc_kernel_ms = 0.f;
-            if (R == 0 || C == 0)
-            {
-                // an empty side: every candidate is 0, and row R's first cell wins (score_overlap_impl)
-                out[p].score = 0;
-                out[p].i_end = R;
-                out[p].j_end = 0;
-            }
-        }
-    };
-    if (bp.empty())
-    {
-        host_pairs();
-        return GSA_SUCCESS;
-    }
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-    std::vector<int32_t> sub((size_t)substsz * (size_t)substsz);
-    if ((e = hipMemcpyAsync(sub.data(), subst, sub.size() * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess)
-        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-    const long long smax = subst_absmax(sub.data(), substsz);
-    if (gsa::krow_score_lds_bytes(substsz) > (size_t)ctx->lds_max) return GSA_ERROR_INVALID_VALUE;
-    // the kernel's own test of the shifted table (nw_kscore_kernel: error bit 2)
-    for (const int32_t v0 : sub)
-    {
-        const long long v = (long long)v0 - gapo - gape;
-        if (v <= -32768 || v > 32767) return GSA_ERROR_INVALID_VALUE;
-    }
-    // rows per lane as score_semi_batch_impl picks them: 4 in both gap models
-    const int kenv = env_int(ctx, "GSA_SCORE_K", 0);
-    const int scoreK = kenv == 2 ? 2 : 4;
-    const int64_t TR = (int64_t)(64 * scoreK) * gsa::kSparseNS;
-    const int nb = (int)bp.size();
-    std::vector<gsa::PairDesc> hd;
-    std::vector<long long> rowOff, colOff;  // ints: the pair's row within kBufBidi, its column within kBufOvCol
-    long long tickets = 0, gran = 0, rowInts = 0, colInts = 0;
-    for (int p : bp)
-    {
-        const int64_t R = pairs[p].adjrows - 1, C = pairs[p].adjcols - 1;
-        // semi_pair_score's tests, per pair
-        bool stripOk = false;
-        const int s = score_ranges(R, C, smax, gapo, gape, 0, &stripOk);
-        if (s != GSA_SUCCESS) return s;
-        if (!stripOk) return GSA_ERROR_INVALID_VALUE;  // span < 2^28: the shifted values' room in int32
-        // the fill keeps 4 x value + source (align_pair_impl's bound)
-        if (forAlign && smax * std::min(R, C) + (long long)(-gapo) + (R + C) * (long long)(-gape) >= gsa::kDbTraceMaxValue)
-            return GSA_ERROR_INVALID_VALUE;
-        gsa::PairDesc d;
-        std::memset(&d, 0, sizeof(d));
-        d.seqY = pairs[p].seqY;
-        d.seqX = pairs[p].seqX;
-        d.R = (int)R;
-        d.C = (int)C;
-        d.Cp = (int)C;
-        d.nTickets = (int)((R + TR - 1) / TR);
-        d.ticketBase = (int)tickets;
-        d.granOff = gran;
-        tickets += d.nTickets;
-        gran += (long long)d.nTickets * gsa::gran_stride(d.Cp);
-        if (tickets > (1ll << 30) || C > (1ll << 30)) return GSA_ERROR_INVALID_VALUE;
-        // row R: columns -kTapPad .. C + 79, as the tap rows
-        rowOff.push_back(rowInts);
-        rowInts += ((long long)gsa::kTapPad + C + 80 + 15) & ~15ll;
-        // column C: the rows 0 ... nTickets TR -- every strip of every ticket stores its K words per lane,
-        // rows past R included, so the pair's last ticket counts whole; a column starts at a multiple of
-        // 16 ints, which keeps every store the alignment it has in the single call
-        colOff.push_back(colInts);
-        colInts += (1 + (long long)d.nTickets * TR + 15) & ~15ll;
-        hd.push_back(d);
-    }
-    // every buffer before anything is launched
-    int s;
-    if ((s = reserve_hard(ctx, ctx->buf[kBufBidi], (size_t)rowInts * sizeof(int))) != GSA_SUCCESS) return s;
-    if ((s = reserve_hard(ctx, ctx->buf[kBufOvCol], (size_t)colInts * sizeof(int))) != GSA_SUCCESS) return s;
-    int* const rows = ctx->buf[kBufBidi].as<int>();
-    int* const cols = ctx->buf[kBufOvCol].as<int>();
-    for (int i = 0; i < nb; ++i)
-    {
-        hd[(size_t)i].score = rows + rowOff[(size_t)i];
-        hd[(size_t)i].hcol = cols + colOff[(size_t)i];
-    }
-    if ((s = ensure_gran(ctx, 2 * (size_t)gran, st)) != GSA_SUCCESS) return s;
-    if ((s = reserve_hard(ctx, ctx->buf[kBufSctl], 64)) != GSA_SUCCESS) return s;
-    // two result words per pair (unused by these modes), then the answers and the error word's
-    const size_t resBytes = (size_t)nb * 2 * sizeof(unsigned long long);
-    const size_t outBytes = ((size_t)nb + 1) * sizeof(gsa::ScoreOut);
-    if ((s = reserve_hard(ctx, ctx->buf[kBufSbatch], resBytes + outBytes, 4096)) != GSA_SUCCESS) return s;
-    const std::vector<int> sched = batch_schedule(ctx, hd, tickets);
-    if ((s = stage_descs(ctx, hd, sched, st)) != GSA_SUCCESS) return s;
-    if (route)
-    {
-        route->K = scoreK;
-        route->granTotal = gran;
-        for (int i = 0; i < nb; ++i)
-        {
-            route->tickets[(size_t)bp[(size_t)i]] = hd[(size_t)i].nTickets;
-            route->granOff[(size_t)bp[(size_t)i]] = hd[(size_t)i].granOff;
-        }
-    }
-    const KeepLaunchRecord keep(ctx);
-    gsa::PairDesc* const ddesc = ctx->buf[kBufDesc].as<gsa::PairDesc>();
-    unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
-    unsigned long long* const sctl = ctx->buf[kBufSctl].as<unsigned long long>();
-    unsigned long long* const res = ctx->buf[kBufSbatch].as<unsigned long long>();
-    gsa::ScoreOut* const dout = (gsa::ScoreOut*)(ctx->buf[kBufSbatch].as<char>() + resBytes);
-    gsa::StripArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.subst = subst;
-    a.substsz = substsz;
-    a.g = gapo;
-    a.go = gapo;
-    a.ge = gape;
-    a.ns = gsa::kSparseNS;
-    a.pairs = ddesc;
-    a.nPairs = nb;
-    a.nTicketsTotal = (int)tickets;
-    a.sched = sched.empty() ? nullptr : (const int*)(ddesc + nb);
-    a.gran = dgran;
-    a.gran2 = dgran + gran;
-    a.ticket = ctx->ctl;
-    a.err = (unsigned*)(sctl + 3);  // the score kernels' own error word (score_ag_strip)
-    a.spin = ctx->spin_ticks;
-    a.swBest = res;
-    a.rowR = rows;  // (every pair's own row and column come from its descriptor)
-    a.tapH = cols;  // (no tap: tapRow stays 0)
-    a.epoch = ++ctx->epoch;
-    if (a.epoch == 0) a.epoch = ++ctx->epoch;
-    if ((e = hipMemsetAsync(ctx->ctl, 0, 4, st)) != hipSuccess || (e = hipMemsetAsync(sctl, 0, 32, st)) != hipSuccess ||
-        (e = hipMemsetAsync(res, 0, resBytes, st)) != hipSuccess)
-        return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-    (void)hipEventRecord(ctx->ev0, st);
-    const int mode = gapo == gape ? gsa::kModeScoreOVL : gsa::kModeScoreOV;
-    // the int8 profile for linear gaps only, as score_semi_batch_impl picks it.  GSA_KROW_Q8=0 / 2: int16 / int8 always
-    const int q8env = env_int(ctx, "GSA_KROW_Q8", 1);
-    a.q8 = (q8env != 0 && (q8env == 2 || mode == gsa::kModeScoreOVL) &&
-            gsa::krow_score_lds_bytes(substsz, true) <= (size_t)ctx->lds_max) ? 1 : 0;
-    a.q8flag = ctx->ctl + 2;
-    // one pair: one workgroup per CU (its tickets are a chain); a batch: all resident slots
-    const int grid = nb == 1 ? std::max(1, std::min((int)tickets, ctx->cu_count)) : 0;
-    if ((e = gsa::launch_krow_score_overlap_batch(a, mode, scoreK, grid, st)) != hipSuccess ||
-        (e = gsa::launch_overlap_max_batch(ddesc, nb, gapo, gape, a.err, dout, st)) != hipSuccess)
-        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-    note_launch(ctx);
-    (void)hipEventRecord(ctx->ev1, st);
-    std::vector<gsa::ScoreOut> ho((size_t)nb + 1);
-    if ((e = hipMemcpyAsync(ho.data(), dout, outBytes, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess)
-        return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    if (batch_ms) *batch_ms = ms;
-    if ((unsigned)ho[(size_t)nb].score != 0) return GSA_ERROR_KERNEL_FAILURE;
-    // a cell of row R or of column C, and never a negative score
-    for (int i = 0; i < nb; ++i)
-    {
-        const gsa::ScoreOut& o = ho[(size_t)i];
-        const int R = hd[(size_t)i].R, C = hd[(size_t)i].C;
-        if (o.score < 0 || o.i_end < 0 || o.i_end > R || o.j_end < 0 || o.j_end > C || (o.i_end != R && o.j_end != C))
-            return GSA_ERROR_KERNEL_FAILURE;
-    }
-    host_pairs();
-    for (int i = 0; i < nb; ++i)
-    {
-        const gsa::ScoreOut& o = ho[(size_t)i];
-        gsa_score_result& r = out[bp[(size_t)i]];
-        r.score = o.score;
-        r.i_end = o.i_end;
-        r.j_end = o.j_end;
-    }
-    return GSA_SUCCESS;
-}
-
-// gsa_align_batch_overlap_dev: every pair's score and end cell from score_overlap_batch_impl, whose
-// checkpoint rows stay in kBufGran, every pair in its own granules; then rounds that fit scratch_limit
-// (nw_pair_overlap_trace_batch_plan.h), bottom-up from each pair's end row's strip: one fill launch over
-// the strips of many pairs, one walk launch with a wave per pair and one small copy back per round
-// (nw_pair_overlap_trace_batch.hip), until every walk stands on row 0 or on column 0; at the end the
-// move bytes of all pairs in one copy, folded into the CIGARs.  gsa_last_launch's record is left as it was.
+// gsa_align_batch_overlap_dev: every pair's score and end cell from score_semi_batch_impl's overlap
+// launch, whose checkpoint rows stay in kBufGran, every pair in its own granules; then trace_batch,
+// bottom-up from each pair's end row's strip, over the pairs whose end cell lies off both free borders
+// and whose one strip fits the limit (the others: the host's answer, or status 1).  gsa_last_launch's
+// record is left as it was.
 int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,
                              int32_t gapo, int32_t gape, int32_t max_workgroups, int64_t scratch_limit,
                              gsa_align_db_result* out, char* cigar, int64_t cigar_cap, int64_t* cigar_need,
@@ -3785,26 +3415,18 @@ int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
     std::memset(res.data(), 0, res.size() * sizeof(gsa_align_db_result));
     std::vector<std::string> cig((size_t)npairs);
     const KeepLaunchRecord keep(ctx);
-    OverlapBatchRoute route;
+    SemiBatchRoute route;
     std::vector<gsa_score_result> sres((size_t)npairs);
-    {
-        const int s = score_overlap_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, true, sres.data(), &inf.score_ms,
-                                               st, &route);
-        if (s != GSA_SUCCESS) return s;
-    }
+    int s = score_semi_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, true, sres.data(), &inf.score_ms, st, &route,
+                                  true);
+    if (s != GSA_SUCCESS) return s;
     const int K = route.K;
     const int KR = K * gsa::kSparseNS;
     const int64_t TR = 64 * (int64_t)KR;
     inf.strip_rows = (int32_t)TR;                    // (0: every pair has an empty side)
     inf.gran_bytes = 16 * (int64_t)route.granTotal;  // both arrays, 8-byte words
     // the traced pairs: an end cell off both free borders, one strip within the limit
-    struct Bp
-    {
-        int p;  // index into pairs
-        int64_t iEnd, jEnd, movOff;
-    };
-    std::vector<Bp> bp;
-    int64_t movTotal = 0;
+    std::vector<BatchTracePair> bp;
     for (int p = 0; p < npairs; ++p)
     {
         gsa_align_db_result& r = res[(size_t)p];
@@ -3824,194 +3446,14 @@ int align_batch_overlap_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* p
             r.i_start = r.j_start = 0;
             continue;
         }
-        bp.push_back(Bp {p, r.i_end, r.j_end, movTotal});
-        movTotal += r.i_end + r.j_end;
+        bp.push_back(BatchTracePair {p, r.i_end, r.j_end, 0, route.granOff[(size_t)p]});
     }
     if (!bp.empty())
     {
-        hipError_t e = hipSuccess;
-        const size_t nb = bp.size();
-        inf.batch_pairs = (int32_t)nb;
-        int sr;
-        if ((sr = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)movTotal, 4096)) != GSA_SUCCESS ||
-            (sr = reserve_hard(ctx, ctx->buf[kBufPairBatchRec], nb * sizeof(gsa::OverlapWalkRec), 4096)) != GSA_SUCCESS)
-            return sr;
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
-        gsa::OverlapWalkRec* const drec = ctx->buf[kBufPairBatchRec].as<gsa::OverlapWalkRec>();
-        unsigned char* const dmoves = ctx->buf[kBufPairMoves].as<unsigned char>();
-        const unsigned long long* const dgran = ctx->buf[kBufGran].as<unsigned long long>();
-        std::vector<gsa::OverlapWalkRec> rec(nb);
-        std::memset(rec.data(), 0, nb * sizeof(gsa::OverlapWalkRec));
-        std::vector<gsa::OverlapBatchPairState> state(nb);
-        for (size_t b = 0; b < nb; ++b)
-        {
-            rec[b].i = (int)bp[b].iEnd;
-            rec[b].j = (int)bp[b].jEnd;
-            rec[b].state = 4u;
-            state[b].tHi = gsa::overlap_end_strip(TR, bp[b].iEnd);
-            state[b].J = bp[b].jEnd;
-            inf.strips += (int32_t)(state[b].tHi + 1);
-        }
-        if ((e = hipMemcpyAsync(drec, rec.data(), nb * sizeof(gsa::OverlapWalkRec), hipMemcpyHostToDevice, st)) != hipSuccess ||
-            (e = hipStreamSynchronize(st)) != hipSuccess)
-            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        std::vector<gsa::OverlapBatchChunk> chunks;
-        std::vector<gsa::PairBatchTask> tasks;
-        std::vector<gsa::PairBatchDesc> descs;
-        std::vector<gsa::OverlapBatchWalk> walks;
-        std::vector<char> blob;
-        for (;;)
-        {
-            const long long used = gsa::overlap_batch_plan_round(TR, limit, state, &chunks);
-            if (chunks.empty())
-            {
-                for (const gsa::OverlapBatchPairState& s : state)
-                    if (s.tHi >= 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);  // (no progress)
-                break;
-            }
-            int s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)used, 4096);
-            if (s != GSA_SUCCESS) return s;
-            unsigned char* const dcodes = ctx->buf[kBufPairCodes].as<unsigned char>();
-            tasks.clear();
-            descs.clear();
-            walks.clear();
-            for (size_t c = 0; c < chunks.size(); ++c)
-            {
-                const gsa::OverlapBatchChunk& ch = chunks[c];
-                const Bp& B = bp[(size_t)ch.pair];
-                const gsa_pair_dev& P = pairs[B.p];
-                gsa::PairBatchDesc d;
-                std::memset(&d, 0, sizeof(d));
-                d.seqY = P.seqY;
-                d.seqX = P.seqX;
-                d.R = P.adjrows - 1;
-                d.iEnd = (int)B.iEnd;
-                d.J = (int)ch.c.J;  // the chunk's last column
-                d.granBase = route.granOff[(size_t)B.p];
-                d.granStride = (long long)gsa::gran_stride(P.adjcols - 1);
-                d.stripBytes = ch.c.stripBytes;
-                descs.push_back(d);
-                for (long long t = ch.c.tLo; t <= ch.c.tHi; ++t)
-                {
-                    gsa::PairBatchTask k;
-                    k.pair = (int)c;
-                    k.strip = (int)t;
-                    k.codeOff = ch.codeOff + gsa::pair_code_off(ch.c, t);
-                    tasks.push_back(k);
-                }
-                gsa::OverlapBatchWalk w;
-                std::memset(&w, 0, sizeof(w));
-                w.seqY = P.seqY;
-                w.seqX = P.seqX;
-                w.codes = dcodes + ch.codeOff;
-                w.stripBytes = ch.c.stripBytes;
-                w.tLo = (int)ch.c.tLo;
-                w.iStop = (int)gsa::pair_chunk_stop_row(TR, ch.c);
-                w.rec = ch.pair;
-                w.moves = dmoves + B.movOff;
-                walks.push_back(w);
-            }
-            // the longest chains first
-            std::stable_sort(tasks.begin(), tasks.end(), [&](const gsa::PairBatchTask& a, const gsa::PairBatchTask& b) {
-                return chunks[(size_t)a.pair].c.J > chunks[(size_t)b.pair].c.J;
-            });
-            // one upload: the task counter (64 bytes, zero), the tasks, the pairs, the walks
-            const size_t oTask = 64, oDesc = oTask + tasks.size() * sizeof(gsa::PairBatchTask),
-                         oWalk = oDesc + descs.size() * sizeof(gsa::PairBatchDesc),
-                         tabBytes = oWalk + walks.size() * sizeof(gsa::OverlapBatchWalk);
-            if ((s = reserve_hard(ctx, ctx->buf[kBufPairBatchTab], tabBytes, 4096)) != GSA_SUCCESS) return s;
-            char* const dtab = ctx->buf[kBufPairBatchTab].as<char>();
-            blob.assign(tabBytes, 0);
-            std::memcpy(blob.data() + oTask, tasks.data(), tasks.size() * sizeof(gsa::PairBatchTask));
-            std::memcpy(blob.data() + oDesc, descs.data(), descs.size() * sizeof(gsa::PairBatchDesc));
-            std::memcpy(blob.data() + oWalk, walks.data(), walks.size() * sizeof(gsa::OverlapBatchWalk));
-            if ((e = hipMemcpyAsync(dtab, blob.data(), tabBytes, hipMemcpyHostToDevice, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-            gsa::OverlapBatchFillArgs f;
-            std::memset(&f, 0, sizeof(f));
-            f.pairs = (const gsa::PairBatchDesc*)(dtab + oDesc);
-            f.tasks = (const gsa::PairBatchTask*)(dtab + oTask);
-            f.ntasks = (int)tasks.size();
-            f.subst = subst;
-            f.substsz = substsz;
-            f.go = gapo;
-            f.ge = gape;
-            f.gran = dgran;
-            f.gran2 = dgran + route.granTotal;
-            f.codes = dcodes;
-            f.counter = (unsigned*)dtab;
-            gsa::OverlapBatchWalkArgs w;
-            std::memset(&w, 0, sizeof(w));
-            w.walks = (const gsa::OverlapBatchWalk*)(dtab + oWalk);
-            w.nwalks = (int)walks.size();
-            w.krShift = KR == 8 ? 3 : 4;
-            w.recs = drec;
-            int grid = 1;
-            const int walkGrid = max_workgroups > 0 ? std::min(w.nwalks, (int)max_workgroups) : w.nwalks;
-            if ((e = gsa::overlap_batch_fill_grid(gapo != gape, KR, f.ntasks, max_workgroups, &grid)) != hipSuccess ||
-                (e = gsa::launch_overlap_batch_trace(f, w, KR, grid, walkGrid, ctx->adbev, st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            note_launch(ctx);
-            if ((e = hipMemcpyAsync(rec.data(), drec, nb * sizeof(gsa::OverlapWalkRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-                (e = hipStreamSynchronize(st)) != hipSuccess)
-                return fail(ctx, e, GSA_ERROR_KERNEL_FAILURE);
-            float m0 = 0.f, m1 = 0.f;
-            (void)hipEventElapsedTime(&m0, ctx->adbev[0], ctx->adbev[1]);
-            (void)hipEventElapsedTime(&m1, ctx->adbev[1], ctx->adbev[2]);
-            inf.fill_ms += m0;
-            inf.walk_ms += m1;
-            inf.rounds += 1;
-            inf.strips_filled += (int32_t)tasks.size();
-            inf.code_bytes = std::max<int64_t>(inf.code_bytes, used);
-            // every record that came back: in range, and done on a free border or on its chunk's upper
-            // boundary right of column 0
-            for (const gsa::OverlapBatchChunk& ch : chunks)
-            {
-                const Bp& B = bp[(size_t)ch.pair];
-                const gsa::OverlapWalkRec& r = rec[(size_t)ch.pair];
-                if (r.n < 0 || r.n > B.iEnd + B.jEnd || r.i < 0 || r.i > B.iEnd || r.j < 0 || r.j > ch.c.J)
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-                if (!gsa::overlap_batch_advance(TR, ch.c, r.i, r.j, r.done != 0, &state[(size_t)ch.pair]))
-                    return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            }
-        }
-        std::vector<unsigned char> mv((size_t)movTotal + 1);
-        if ((e = hipMemcpyAsync(mv.data(), dmoves, (size_t)movTotal, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-            (e = hipStreamSynchronize(st)) != hipSuccess)
-            return fail(ctx, e, GSA_ERROR_MEMORY_TRANSFER);
-        for (size_t b = 0; b < nb; ++b)
-        {
-            gsa_align_db_result& r = res[(size_t)bp[b].p];
-            if (rec[b].i != 0 && rec[b].j != 0) return fail(ctx, hipErrorUnknown, GSA_ERROR_KERNEL_FAILURE);
-            cig[(size_t)bp[b].p] = fold_cigar(mv.data() + bp[b].movOff, rec[b].n);
-            r.i_start = rec[b].i;
-            r.j_start = rec[b].j;
-            r.status = 0;
-        }
+        const BatchTrace t {pairs, subst, substsz, gapo, gape, 0, max_workgroups, KR, route.granTotal, limit};
+        if ((s = trace_batch<OverlapBatchTrace>(ctx, t, bp, &inf, res.data(), cig.data(), st)) != GSA_SUCCESS) return s;
     }
-    // the strings back to back in pair order; a pair's offset does not depend on the buffer's size
-    int64_t at = 0;
-    for (int p = 0; p < npairs; ++p)
-    {
-        gsa_align_db_result& r = res[(size_t)p];
-        const int64_t len = (int64_t)cig[(size_t)p].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
-        out[p] = r;
-    }
-    if (cigar_need) *cigar_need = at;
-    if (info) *info = inf;
+    finish_batch(res, cig, inf, out, cigar, cigar_cap, cigar_need, info);
     if (kernel_ms) *kernel_ms = inf.score_ms + inf.fill_ms + inf.walk_ms;
     return GSA_SUCCESS;
 }
@@ -4124,8 +3566,7 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
         if (codes && ((s = reserve_hard(ctx, ctx->buf[kBufPairCodes], (size_t)plan.codeBytes, 4096)) != GSA_SUCCESS ||
                       (s = reserve_hard(ctx, ctx->buf[kBufPairMoves], (size_t)(R + C), 4096)) != GSA_SUCCESS))
             return s;
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        if (const int es = ensure_trace_events(ctx); es != GSA_SUCCESS) return es;
         char* const meta = ctx->buf[kBufPairMeta].as<char>();
         gsa::BandWalkRec* const drec = (gsa::BandWalkRec*)(meta + 64);
         gsa::BandDesc* const ddesc = (gsa::BandDesc*)(meta + 128);
@@ -4211,18 +3652,8 @@ int band_impl(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, const int32_t*
         sout->calc_kernel_ms = inf.score_ms;
         return GSA_SUCCESS;
     }
-    if (r.status == 0)
-    {
-        const int64_t len = (int64_t)cig.size();
-        if (len + 1 <= cigar_cap)
-        {
-            std::memcpy(cigar, cig.c_str(), (size_t)len + 1);
-            r.cigar_len = len;
-        }
-        else
-            r.status = 2;
-        if (cigar_need) *cigar_need = len + 1;
-    }
+    const int64_t need = pack_cigars(&r, &cig, 1, cigar, cigar_cap);
+    if (cigar_need) *cigar_need = need;
     *out = r;
     if (info) *info = inf;
     if (kernel_ms) *kernel_ms = inf.score_ms + inf.walk_ms;
@@ -4364,8 +3795,7 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
     if (anyDev)
     {
         inf.strip_rows = gsa::kBandTR;
-        for (hipEvent_t& ev : ctx->adbev)
-            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(ctx, e, GSA_ERROR_CUDA_GENERAL);
+        if (const int es = ensure_trace_events(ctx); es != GSA_SUCCESS) return es;
     }
     // launch 0: the pairs without codes; then the rounds
     std::vector<char> blob, back;
@@ -4509,24 +3939,11 @@ int band_batch_impl(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, con
         if (kernel_ms) *kernel_ms = inf.nocode_ms;
         return GSA_SUCCESS;
     }
-    int64_t at = 0;
+    const int64_t at = pack_cigars(res.data(), cig.data(), npairs, cigar, cigar_cap);
     for (int p = 0; p < npairs; ++p)
     {
-        gsa_align_db_result& r = res[(size_t)p];
+        const gsa_align_db_result& r = res[(size_t)p];
         const Bp& b = bp[(size_t)p];
-        const int64_t len = (int64_t)cig[(size_t)p].size();
-        if (r.status == 0)
-        {
-            if (at + len + 1 <= cigar_cap)
-            {
-                std::memcpy(cigar + at, cig[(size_t)p].c_str(), (size_t)len + 1);
-                r.cigar_off = at;
-                r.cigar_len = len;
-            }
-            else
-                r.status = 2;
-            at += len + 1;
-        }
         out[p] = r;
         if (pair_info)
         {
@@ -4657,8 +4074,8 @@ int gsa_score_overlap_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev
                                 int32_t gapo, int32_t gape, gsa_score_result* out, float* batch_kernel_ms, void* stream)
 {
     if (!ctx) return GSA_ERROR_INVALID_VALUE;
-    return score_overlap_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, false, out, batch_kernel_ms,
-                                    pick_stream(ctx, stream));
+    return score_semi_batch_impl(ctx, npairs, pairs, subst, substsz, gapo, gape, false, out, batch_kernel_ms,
+                                 pick_stream(ctx, stream), nullptr, true);
 }
 
 int gsa_align_batch_semi_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst, int32_t substsz,

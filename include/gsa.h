@@ -945,9 +945,10 @@ int gsa_align_pair_semi_dev(gsa_ctx* ctx, const int32_t* seqY, int32_t adjrows, 
  * gsa_mem_stats.
  * The mode has no second path, so no pair is routed elsewhere: it is errorInvalidValue, before
  * anything is enqueued, for everything gsa_score_batch_dev rejects and when any one pair is a pair
- * gsa_score_semi_dev refuses (its four conditions).  The call adds no launch kind and no knob, leaves
- * the record of gsa_last_launch and the fills' sticky error word alone, and reports kernel errors in
- * the score kernels' own control word.  An end column outside 0 ... C is errorKernelFailure. */
+ * gsa_score_semi_dev refuses (its four conditions); out is then left as it was, the entries of the
+ * pairs with an empty side included.  The call adds no launch kind and no knob, leaves the record of
+ * gsa_last_launch and the fills' sticky error word alone, and reports kernel errors in the score
+ * kernels' own control word.  An end column outside 0 ... C is errorKernelFailure. */
 int gsa_score_semi_batch_dev(gsa_ctx* ctx, int32_t npairs, const gsa_pair_dev* pairs, const int32_t* subst,
                              int32_t substsz, int32_t gapo, int32_t gape, gsa_score_result* out,
                              float* batch_kernel_ms, void* stream);

@@ -44,7 +44,7 @@ int main()
     while (std::scanf("%lld %lld %llu %d", &TR, &limit, &seed, &npairs) == 4)
     {
         std::vector<In> in((size_t)npairs);
-        std::vector<gsa::OverlapBatchPairState> st((size_t)npairs);
+        std::vector<gsa::BatchPairState> st((size_t)npairs);
         std::vector<long long> next_strip((size_t)npairs);
         for (int p = 0; p < npairs; ++p)
         {
@@ -60,13 +60,13 @@ int main()
             if (gsa::pair_strip_bytes(TR, q.jEnd) > limit) bad(kase, "a strip of the input exceeds the limit");
         }
         std::printf("case %d\n", npairs);
-        std::vector<gsa::OverlapBatchChunk> chunks;
+        std::vector<gsa::BatchChunk> chunks;
         long long rounds = 0;
         for (;;)
         {
-            const long long used = gsa::overlap_batch_plan_round(TR, limit, st, &chunks);
+            const long long used = gsa::batch_plan_round(TR, limit, st, &chunks);
             bool active = false;
-            for (const gsa::OverlapBatchPairState& s : st) active = active || s.tHi >= 0;
+            for (const gsa::BatchPairState& s : st) active = active || s.tHi >= 0;
             if (chunks.empty())
             {
                 if (active) bad(kase, "a round with active pairs fills no strip");
@@ -78,16 +78,16 @@ int main()
             // the fixed order: remaining bytes descending, ties by index (over the pairs that got a chunk)
             for (size_t c = 1; c < chunks.size(); ++c)
             {
-                const long long a = gsa::overlap_batch_pair_remaining(TR, st[(size_t)chunks[c - 1].pair]);
-                const long long b = gsa::overlap_batch_pair_remaining(TR, st[(size_t)chunks[c].pair]);
+                const long long a = gsa::batch_pair_remaining(TR, st[(size_t)chunks[c - 1].pair]);
+                const long long b = gsa::batch_pair_remaining(TR, st[(size_t)chunks[c].pair]);
                 if (a < b || (a == b && chunks[c - 1].pair > chunks[c].pair)) bad(kase, "pairs out of order");
             }
             std::vector<std::pair<long long, long long>> spans;
             long long sum = 0;
             std::vector<char> seen((size_t)npairs, 0);
-            for (const gsa::OverlapBatchChunk& b : chunks)
+            for (const gsa::BatchChunk& b : chunks)
             {
-                const gsa::OverlapBatchPairState& s = st[(size_t)b.pair];
+                const gsa::BatchPairState& s = st[(size_t)b.pair];
                 if (seen[(size_t)b.pair]) bad(kase, "a pair twice in a round");
                 seen[(size_t)b.pair] = 1;
                 if (b.c.tHi != next_strip[(size_t)b.pair] || b.c.tHi != s.tHi || b.c.tLo < 0 || b.c.tLo > b.c.tHi)
@@ -120,10 +120,10 @@ int main()
                     bad(kase, "one pair: not overlap_plan_chunk's chunk");
             }
             // the walks
-            for (const gsa::OverlapBatchChunk& b : chunks)
+            for (const gsa::BatchChunk& b : chunks)
             {
                 const In& q = in[(size_t)b.pair];
-                gsa::OverlapBatchPairState& s = st[(size_t)b.pair];
+                gsa::BatchPairState& s = st[(size_t)b.pair];
                 const long long stop = gsa::pair_chunk_stop_row(TR, b.c);
                 long long i, j;
                 bool done;
@@ -157,7 +157,7 @@ int main()
                 }
             }
         }
-        for (const gsa::OverlapBatchPairState& s : st)
+        for (const gsa::BatchPairState& s : st)
             if (s.tHi >= 0) bad(kase, "a pair's walk did not end");
         std::printf("end %lld\n", rounds);
         ++kase;

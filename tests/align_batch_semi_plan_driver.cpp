@@ -35,7 +35,7 @@ int main()
     int npairs;
     while (std::scanf("%lld %lld %llu %d", &TR, &limit, &seed, &npairs) == 4)
     {
-        std::vector<gsa::SemiBatchPairState> st((size_t)npairs);
+        std::vector<gsa::BatchPairState> st((size_t)npairs);
         std::vector<long long> next_strip((size_t)npairs);
         for (int p = 0; p < npairs; ++p)
         {
@@ -49,13 +49,13 @@ int main()
             if (gsa::pair_strip_bytes(TR, jEnd - jW) > limit) bad(kase, "a strip of the input exceeds the limit");
         }
         std::printf("case %d\n", npairs);
-        std::vector<gsa::SemiBatchChunk> chunks;
+        std::vector<gsa::BatchChunk> chunks;
         long long rounds = 0;
         for (;;)
         {
-            const long long used = gsa::semi_batch_plan_round(TR, limit, st, &chunks);
+            const long long used = gsa::batch_plan_round(TR, limit, st, &chunks);
             bool active = false;
-            for (const gsa::SemiBatchPairState& s : st) active = active || s.tHi >= 0;
+            for (const gsa::BatchPairState& s : st) active = active || s.tHi >= 0;
             if (chunks.empty())
             {
                 if (active) bad(kase, "a round with active pairs fills no strip");
@@ -67,16 +67,16 @@ int main()
             // the fixed order: remaining bytes descending, ties by index (over the pairs that got a chunk)
             for (size_t c = 1; c < chunks.size(); ++c)
             {
-                const long long a = gsa::semi_batch_pair_remaining(TR, st[(size_t)chunks[c - 1].pair]);
-                const long long b = gsa::semi_batch_pair_remaining(TR, st[(size_t)chunks[c].pair]);
+                const long long a = gsa::batch_pair_remaining(TR, st[(size_t)chunks[c - 1].pair]);
+                const long long b = gsa::batch_pair_remaining(TR, st[(size_t)chunks[c].pair]);
                 if (a < b || (a == b && chunks[c - 1].pair > chunks[c].pair)) bad(kase, "pairs out of order");
             }
             std::vector<std::pair<long long, long long>> spans;
             long long sum = 0;
             std::vector<char> seen((size_t)npairs, 0);
-            for (const gsa::SemiBatchChunk& b : chunks)
+            for (const gsa::BatchChunk& b : chunks)
             {
-                const gsa::SemiBatchPairState& s = st[(size_t)b.pair];
+                const gsa::BatchPairState& s = st[(size_t)b.pair];
                 if (seen[(size_t)b.pair]) bad(kase, "a pair twice in a round");
                 seen[(size_t)b.pair] = 1;
                 if (b.c.tHi != next_strip[(size_t)b.pair] || b.c.tHi != s.tHi || b.c.tLo < 0 || b.c.tLo > b.c.tHi)
@@ -109,9 +109,9 @@ int main()
             }
             // the walks: a semi-global path always reaches row 0, so a pair is done only once its chunk
             // holds strip 0; else it stands on the chunk's upper boundary at a column of its window
-            for (const gsa::SemiBatchChunk& b : chunks)
+            for (const gsa::BatchChunk& b : chunks)
             {
-                gsa::SemiBatchPairState& s = st[(size_t)b.pair];
+                gsa::BatchPairState& s = st[(size_t)b.pair];
                 if (b.c.tLo == 0)
                 {
                     s.tHi = -1;
@@ -124,7 +124,7 @@ int main()
                 next_strip[(size_t)b.pair] = s.tHi;
             }
         }
-        for (const gsa::SemiBatchPairState& s : st)
+        for (const gsa::BatchPairState& s : st)
             if (s.tHi >= 0) bad(kase, "a pair was not filled up to strip 0");
         std::printf("end %lld\n", rounds);
         ++kase;

@@ -90,6 +90,34 @@ def test_int16_table_edges(engine, golden):
             assert ei.value.stat == gsa.NwStat.errorInvalidValue
 
 
+def test_refused_call_leaves_out_untouched(engine, golden):
+    """Three pairs, the middle one with an empty side.  With a table the call refuses (s - gapo - gape at
+    -32768, as in test_int16_table_edges) every word of out stays as it was, the host-answered pair's
+    too; with a good table the three are scored as the reference says, the empty side on the host."""
+    go, ge = -11, -1
+    Y, X = sb.related(120, 260, 43)
+    base = np.asarray(golden.blosum62).reshape(25, 25).astype(np.int64)
+    bad_sub = base.copy()
+    bad_sub[int(Y[5]), int(X[70])] = -32768 + go + ge
+    good, bad = sb.Batch("keep", base), sb.Batch("refuse", bad_sub)
+    for b in (good, bad):
+        b.add("s", sb.seq(60, 3), sb.seq(80, 4))
+        b.add("e", hdr([]), sb.seq(80, 5))
+        b.add("t", sb.seq(70, 7), sb.seq(50, 8))
+    arr = (gsa.PairDev * 3)()
+    for k, (yp, ar, xp, ac) in enumerate(bad.ptrs()):
+        arr[k].seqY, arr[k].adjrows, arr[k].seqX, arr[k].adjcols = yp, ar, xp, ac
+    assert (arr[1].adjrows, arr[1].adjcols) == (1, 81)
+    res = (gsa.ScoreResult * 3)()
+    for r in res:
+        r.score, r.i_end, r.j_end = -77, -78, -79
+    st = gsa.lib().gsa_score_semi_batch_dev(engine._h, 3, arr, *bad.table(), go, ge, res, None, None)
+    assert st == gsa.NwStat.errorInvalidValue
+    assert [(r.score, r.i_end, r.j_end) for r in res] == [(-77, -78, -79)] * 3
+    sc = _check_scores(engine, good, go, ge, align=sp.align64)
+    assert sc[1] == (0, 0, 0)  # R = 0; R > 0 with C = 0 is test_edges_in_one_batch's "C0": gapo + (R - 1) gape at (R, 0)
+
+
 @pytest.fixture(scope="module")
 def few(engine, golden):
     b = sb.Batch("few", golden.blosum62)
